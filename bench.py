@@ -2,6 +2,7 @@
 """Contract benchmark: patches/s of the per-slide VLSA forward (language-guided patch aggregation).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also writes the last timed step's logits / incidence / vhat as DIR/*.npy)
 
 A STEP = one pass of the hot path over one batch of 128 HBM-resident bags, issued as TWO launches of 64 bags (64 = the most
 the persistent kernels take per launch; the reference's eval loop is a stream of independent bags, its optimizer step 32 of
@@ -249,6 +250,18 @@ def load_pmc():
     return None, None
 
 
+def dump_outputs(out_dir, plans, launches):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- logits [B, K], incidence [B, K] and unit
+    image features vhat [B, D] of each of the step's launches still held by its plan (one plan per stream; a plan keeps the last
+    launch it ran), stacked launch after launch in issue order, float32, one DIR/<name>.npy each.  Rows: BAGS_PER_LAUNCH x
+    min(streams, LAUNCHES_PER_STEP) -- 128 at the defaults, 64 with --streams 1; every launch of a step reads the same bags."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("logits", "incidence", "vhat"):
+        arr = torch.cat([getattr(plans[i % len(plans)], name).float().cpu() for i in launches]).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def oracle_check(X, Q, T, ls, W, b, want_attn=False):
     """CPU oracle (restatement of the reference's op sequence) on one bag: fp32 math on the values the kernel read."""
     from oracle import vlsa_oracle as O
@@ -267,7 +280,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (with_attn / configs[1] / single_slide / "
                                                             "strong_scaling_base at N = 1, weak_scaling at N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the headline's last timed step to DIR/<name>.npy (float32): logits, incidence, vhat "
+                         "of each of its launches still held by a stream's plan -- 128 rows with the default 2 streams, 64 with "
+                         "--streams 1 (both launches of a step read the same 64 bags)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -410,11 +429,12 @@ def main():
         torch.cuda.synchronize()
 
     def measure(rows_local, rows_global, K, steps, warmup, seed, roofline, dtype=torch.bfloat16, want_attn=False, verify_every=1,
-                plane=None):
+                plane=None, dump=None):
         """K-class head, BPL bags of `rows_local` rows (bf16 or fp32) on this rank (`rows_global` over all ranks); want_attn: the
         same launches also hand out every bag's attention weights A [P, N] (N = 1 only).  Returns (seconds of `steps` steps = max
         over ranks, roofline dict or None, info dict).  roofline = True also binds the timed launches to the CPU oracle: logits of
-        every `verify_every`-th bag of the LAST timed launch (and, with want_attn, all of A for its first and last bag)."""
+        every `verify_every`-th bag of the LAST timed launch (and, with want_attn, all of A for its first and last bag).
+        dump: a directory for the outputs of the last timed step (rank 0; dump_outputs)."""
         bags = synth_bags(device, seed, BPL, rows_local, dtype)
         esz = bags[0].element_size()
         Q, T, W, b, ls = synth_params(device, K)
@@ -463,6 +483,9 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump and rank == 0:
+            held = {i % NS: i for i in range(n_last - LPS, n_last)}          # plan -> the last launch of the step it ran
+            dump_outputs(dump, plans, sorted(held.values()))
 
         roof = None
         bytes_pp = D * esz + (4 * P if want_attn else 0)     # 1024 B (bf16) / 2048 B (fp32) read, + 4 P written with A
@@ -975,7 +998,7 @@ def main():
     if world == 1 and not force_sharded:
         cfg, scaling = "configs[2]", "strong"
         rows, K = CONFIGS[cfg]["rows"], CONFIGS[cfg]["K"]
-        dt, roof, info = measure(rows, rows, K, a.steps, a.warmup, 100, True)
+        dt, roof, info = measure(rows, rows, K, a.steps, a.warmup, 100, True, dump=a.dump_outputs)
         total = BPL * LPS * rows * a.steps
         workload = (f"{cfg}: synthetic 50k x 512 bf16 bags, P=12 queries, K=4 rank prompts, mean pooling + Linear(512,512) "
                     f"head; one step = {BPL * LPS} bags = {LPS} launches of {BPL} distinct bags")
@@ -1023,7 +1046,7 @@ def main():
             working = [pick] + [c for c in working if c is not pick]
             chosen = pick
             data_plane.update(chosen=pick[2], also_working=[n for _, _, n in working[1:]], trial_ms_per_step={k: round(v, 4) for k, v in trial.items()})
-        dt, roof, info = measure(hi - lo, rows, K, a.steps, a.warmup, 100 + rank, True, verify_every=4)
+        dt, roof, info = measure(hi - lo, rows, K, a.steps, a.warmup, 100 + rank, True, verify_every=4, dump=a.dump_outputs)
         total = BPL * LPS * rows * a.steps
         workload = (f"{cfg}: synthetic 200k x 512 bf16 bags, P=12, K=8, patch-sharded over {world} GPUs ({rows // world} rows per "
                     f"GPU per bag), records to their bag owners + packed results to everyone per launch ({chosen[2]}); one step = "

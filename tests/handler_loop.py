@@ -7,8 +7,8 @@ exactly the way ``runner/vlsa_handler.py`` drives it on a box that has no refere
     update_network(...)         runner/vlsa_handler.py:260-289  per-bag forward, cat, objective, backward, step
     test_model(...)             runner/vlsa_handler.py:315-345  eval mode, per-bag forward under no_grad, softmax
 
-tests/test_construction_cpu.py additionally runs the reference's REAL ``func_load_model`` against the patched factory when
-/root/reference is present."""
+tests/test_construction_cpu.py drives ``build_model`` through ``patch_reference`` on stand-in modules with the reference's names;
+tests/test_deferred_cpu.py drives ``update_network`` on deferred outputs."""
 from __future__ import annotations
 
 import torch

@@ -6,13 +6,14 @@ The tokenizer and the pretrained VL model come through the package's hooks (synt
 """
 import json
 import os
+import sys
 import tempfile
+import types
 
 import pytest
 import torch
 import torch.nn as nn
 
-import _ref_import
 import handler_cases as HC
 import handler_loop as HL
 
@@ -148,53 +149,78 @@ def test_invalid_names_raise_like_the_reference(hooks_installed):
             load_model("VLSA", **a)
 
 
-@pytest.mark.skipif(not _ref_import.reference_available(), reason="needs the reference checkout (build container only)")
-def test_reference_handler_builds_the_hip_model_after_one_line_patch(hooks_installed):
-    """``patch_reference()`` and then the reference's REAL, unmodified ``VLSAHandler.func_load_model(cfg)``: it returns this
-    package's VLSA with the reference model's saved key set."""
-    _ref_import.import_reference()
-    cwd = os.getcwd()
-    os.chdir(_ref_import.REF_ROOT)
-    import model.deepmil as ref_mil
-    import model.utils as ref_utils
-    import model.vlsa as ref_vlsa
-    from runner.vlsa_handler import VLSAHandler
+def _stand_in_modules(monkeypatch, names):
+    """empty modules registered under the reference's module names (sys.modules entries and parent attributes restored by
+    monkeypatch): what ``patch_reference`` reaches for, without the reference's source"""
+    mods = {}
+    for name in names:
+        parts = name.split(".")
+        for k in range(1, len(parts) + 1):
+            full = ".".join(parts[:k])
+            if full not in mods:
+                mods[full] = types.ModuleType(full)
+                monkeypatch.setitem(sys.modules, full, mods[full])
+                if k > 1:
+                    setattr(mods[".".join(parts[:k - 1])], parts[k - 1], mods[full])
+    return mods
+
+
+def test_patch_reference_points_the_factory_at_this_package_and_unpatch_restores_it(hooks_installed, monkeypatch):
+    """``patch_reference()`` re-points the names the reference's factory looks up -- ``model.utils.VLSA`` / ``model.vlsa.VLSA``
+    (model/utils.py:36,44) and ``model.deepmil.{VLFAN, FeatMIL, DeepMIL, logit_pooling}`` -- at this package's classes, so a factory
+    that resolves ``VLSA`` at call time builds the HIP model with the reference model's saved key set; it switches the handler's
+    training loop to deferred calls; ``unpatch_reference`` puts every name and the flag back."""
+    from vlsa_amd import deepmil as fast
     from vlsa_amd.model_utils import patch_reference, unpatch_reference
     from vlsa_amd.vlsa import VLSA
+    mods = _stand_in_modules(monkeypatch, ["model.utils", "model.vlsa", "model.deepmil"])
+    originals = {}
+    for mod, attr in (("model.utils", "VLSA"), ("model.vlsa", "VLSA"), ("model.deepmil", "VLFAN"), ("model.deepmil", "FeatMIL"),
+                      ("model.deepmil", "DeepMIL"), ("model.deepmil", "logit_pooling")):
+        originals[mod, attr] = type(f"Original_{attr}", (), {})
+        setattr(mods[mod], attr, originals[mod, attr])
+    # model.vlsa imports logit_pooling from model.deepmil: one object under two names
+    originals["model.vlsa", "logit_pooling"] = mods["model.vlsa"].logit_pooling = originals["model.deepmil", "logit_pooling"]
+    ref_utils = mods["model.utils"]
+
+    def load_model(arch, **kw):                       # the factory's dispatch: the class is looked up when it is called
+        assert arch == "VLSA"
+        return ref_utils.VLSA(**kw)
     saved = patch_reference()
     try:
+        assert ref_utils.VLSA is VLSA and mods["model.vlsa"].VLSA is VLSA
+        dm = mods["model.deepmil"]
+        assert (dm.VLFAN, dm.FeatMIL, dm.DeepMIL) == (fast.VLFAN, fast.FeatMIL, fast.DeepMIL)
+        assert dm.logit_pooling is fast.logit_pooling and mods["model.vlsa"].logit_pooling is fast.logit_pooling
+        assert VLSA.defer_training_calls is True
         with tempfile.TemporaryDirectory() as tmp:
             p_init, p_proto = HC.write_prompt_files(tmp)
-            model = VLSAHandler.func_load_model(HC.make_cfg(p_init, p_proto))
+            model = HL.build_model(HC.make_cfg(p_init, p_proto), load_model)
     finally:
-        assert VLSA.defer_training_calls is True                      # (patch_reference switches the handler's training loop to deferred calls)
         unpatch_reference(saved)
-        assert VLSA.defer_training_calls is False and ref_utils.VLSA is saved["VLSA_utils"] and ref_mil.VLFAN is saved["VLFAN"]
-        os.chdir(cwd)
+    assert VLSA.defer_training_calls is False
+    for (mod, attr), cls in originals.items():
+        assert getattr(mods[mod], attr) is cls, (mod, attr)
     assert isinstance(model, VLSA)
     ref = json.load(open(os.path.join(GOLDEN, "handler_keys.json")))
     assert {k: list(v.shape) for k, v in model.state_dict().items() if "prompt_encoder" not in k} == ref["saved"]
     assert sorted(n for n, p in model.named_parameters() if p.requires_grad) == ref["requires_grad"]
 
 
-@pytest.mark.skipif(not _ref_import.reference_available(), reason="needs the reference checkout (build container only)")
-def test_patch_reference_can_make_the_handlers_datasets_resident(hooks_installed):
-    """``patch_reference(resident_bags=True)``: the dataset factory the reference's handlers call
-    (runner/sa_handler.py:111-116 -> dataset/utils.py prepare_surv_dataset) hands back its dataset wrapped in ResidentBags."""
-    _ref_import.import_reference()
-    cwd = os.getcwd()
-    os.chdir(_ref_import.REF_ROOT)
-    import dataset.utils as ref_ds
-    import model.deepmil as ref_mil
-    import model.utils as ref_utils
-    import model.vlsa as ref_vlsa
-    import runner.sa_handler as ref_sa
+def test_patch_reference_can_make_the_handlers_dataset_factory_resident(monkeypatch):
+    """``patch_reference(resident_bags=True)``: the dataset factory the reference's handlers call (``dataset.utils.prepare_surv_dataset``,
+    imported by name into ``runner.sa_handler``) hands back its dataset wrapped in ResidentBags; patching twice does not wrap twice;
+    ``unpatch_reference`` restores both names."""
     from vlsa_amd.ingest import ResidentBags
-    from vlsa_amd.model_utils import patch_reference
-    original = ref_ds.prepare_surv_dataset
-    assert ref_sa.prepare_surv_dataset is original
-    ref_ds.prepare_surv_dataset = lambda *a, **k: ("a dataset", a, k)      # stands in for the file-reading factory
-    ref_sa.prepare_surv_dataset = ref_ds.prepare_surv_dataset
+    from vlsa_amd.model_utils import patch_reference, unpatch_reference
+    mods = _stand_in_modules(monkeypatch, ["model.utils", "model.vlsa", "model.deepmil", "dataset.utils", "runner.sa_handler"])
+    for mod, attrs in (("model.utils", ("VLSA",)), ("model.vlsa", ("VLSA",)), ("model.deepmil", ("VLFAN", "FeatMIL", "DeepMIL", "logit_pooling"))):
+        for attr in attrs:
+            setattr(mods[mod], attr, object())
+    mods["model.vlsa"].logit_pooling = mods["model.deepmil"].logit_pooling
+    ref_ds, ref_sa = mods["dataset.utils"], mods["runner.sa_handler"]
+    original = lambda *a, **k: ("a dataset", a, k)      # noqa: E731  (stands in for the file-reading factory)
+    ref_ds.prepare_surv_dataset = ref_sa.prepare_surv_dataset = original
     saved = patch_reference(resident_bags=True, dtype=torch.float32)
     try:
         out = ref_sa.prepare_surv_dataset(["p1"], {"cfg": 1}, meta_data=None)
@@ -204,10 +230,8 @@ def test_patch_reference_can_make_the_handlers_datasets_resident(hooks_installed
         patch_reference(resident_bags=True)                                # idempotent: not wrapped twice
         assert not isinstance(ref_sa.prepare_surv_dataset(["p1"], {}).dataset, ResidentBags)
     finally:
-        from vlsa_amd.model_utils import unpatch_reference
         unpatch_reference(saved)
-        ref_ds.prepare_surv_dataset = ref_sa.prepare_surv_dataset = original
-        os.chdir(cwd)
+    assert ref_ds.prepare_surv_dataset is original and ref_sa.prepare_surv_dataset is original
 
 
 def test_func_load_model_and_the_run_directory_loader(hooks_installed):

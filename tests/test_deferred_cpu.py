@@ -114,36 +114,28 @@ def test_materialisation_runs_with_gradients_enabled():
     assert m.w.grad is not None and m.w.grad.abs().sum() > 0
 
 
-import _ref_import  # noqa: E402
-
-
-@pytest.mark.skipif(not _ref_import.reference_available(), reason="needs the reference checkout (build container only)")
-def test_the_reference_handlers_own_update_network_runs_on_deferred_outputs():
-    """``VLSAHandler._update_network`` itself (runner/vlsa_handler.py:260-289, unbound, on a stand-in handler object): its
-    ``pred, *_ = self.net(xs[i])`` loop records, its ``torch.cat(y_hat, dim=0)`` runs the ONE batched call, its backward and optimizer
+def test_the_handlers_per_bag_update_loop_runs_on_deferred_outputs():
+    """The reference handler's training step, restated in tests/handler_loop.py (runner/vlsa_handler.py:260-289): its per-bag
+    ``net(x)[0]`` calls record, its ``torch.cat`` of the predictions runs the ONE batched call, its objective, backward and optimizer
     step see the batched graph."""
-    import os
-    import types
-    cwd = os.getcwd()
-    _ref_import.import_reference()
-    try:
-        os.chdir(_ref_import.REF_ROOT)
-        from runner.vlsa_handler import VLSAHandler
-    finally:
-        os.chdir(cwd)
-    m, bags = _Stub(), _bags(4)
+    import handler_loop as HL
+
+    class _Net(_Stub):
+        def get_logit_scale(self):
+            return torch.tensor(1.0)
+    m, bags = _Net(), _bags(4)
     ys = [torch.tensor([[float(i), 1.0]]) for i in range(4)]
     opt = torch.optim.SGD([m.w], lr=0.1)
     seen = {}
 
-    def calc_objective_loss(raw_pred, label):
-        seen["pred"], seen["label"] = raw_pred, label
+    def objective(raw_pred, t, c, scale):
+        seen["pred"], seen["t"], seen["c"] = raw_pred, t, c
         return (raw_pred * raw_pred).mean()
-    handler = types.SimpleNamespace(net=m, optimizer=opt, calc_objective_loss=calc_objective_loss)
     w0 = m.w.detach().clone()
-    val_loss, val_preds = VLSAHandler._update_network(handler, bags, ys)
+    val_loss, val_preds = HL.update_network(m, opt, objective, bags, ys)
     assert m.calls == 1                                                     # four net(x) calls, ONE evaluation
-    assert type(seen["pred"]) is torch.Tensor and tuple(seen["pred"].shape) == (4, 3) and tuple(seen["label"].shape) == (4, 2)
+    assert type(seen["pred"]) is torch.Tensor and tuple(seen["pred"].shape) == (4, 3)
+    assert torch.equal(seen["t"], torch.arange(4.0)) and torch.equal(seen["c"], torch.ones(4))
     ref = _Stub()
     logits = ref.forward_bags(bags)[0]
     loss = (logits * logits).mean()

@@ -1,4 +1,4 @@
-"""The three exchanges of the patch-sharded batch plan (vlsa_amd/sharded.py) with 2 / 4 / 8 PROCESSES sharing ONE GPU: "owner"
+"""The three exchanges of the patch-sharded batch plan (vlsa_amd/sharded.py) with 2 / 4 / 5 PROCESSES sharing ONE GPU: "owner"
 (all_to_all_single of the records to their bag owners + all-gather of the packed results, here over gloo: RCCL refuses two ranks on a
 device), "ipc" (kernels storing into peer buffers mapped through hipIpc, epoch flags, acknowledgement gates: csrc/xchg.hip -- the real
 transport, IPC works between processes on one device) and "allgather" (rounds 1-4).  Every rank must reproduce the unsharded batch
@@ -103,7 +103,8 @@ def _worker(rank, world, port, ret):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+# at most 5 ranks: with the pytest process itself that is 6 processes holding the GPU open, the most a shared device may carry
+@pytest.mark.parametrize("world", [2, 4, 5])
 def test_exchanges_on_one_gpu_reproduce_the_unsharded_result(world):
     mgr = mp.Manager()
     ret = mgr.dict()
