@@ -680,6 +680,29 @@ int vlsa_prepare_attn_dx_weights(const float* Wa, const float* Wg, int gated, vo
 int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep, const void* prep_t,
                                  int gated, const int* tile_start, int n_tiles, const float* da, const float* aw, const float* dpooled,
                                  const int64_t* a_off, float drop_p, unsigned int seed, void* stream);
+/* Batched DeepMIL training (up to 64 bags per call, one dtype, D = 512, 512 -> 256 hidden).  Dropout seeds come from a DEVICE word
+ * seed_word (int64, low 32 bits used) that an in-stream op advances between training forwards, so that a captured graph replays new
+ * masks; bag b of a call draws its masks under bag_drop_seed(seed, b) = seed for b = 0, a hash of (seed, b) otherwise -- a batch of
+ * one bag has the masks of vlsa_gated_scores_train(seed).
+ * vlsa_gated_scores_batch_train: vlsa_gated_scores_batch with the gated module's training-mode dropout (drop_p; 0: inference, then
+ *   seed_word may be NULL).
+ * vlsa_attn_pool_backward_batch: backward of pooled_b = softmax_b(a) X_b through the scores in ONE pass over the rows (+ two fixed-
+ *   order reductions): da_n = w_n (x_n - pooled_b) . dpooled_b is formed in the tile prologue.  a_raw: raw scores (bag b at a_off[b]);
+ *   m2 / l: per-bag softmax max (exp2 domain) and sum at stride m_stride; pooled / dpooled [B][512].  dW / dvec / ws as
+ *   vlsa_attn_scores_backward (summed over the bags); da_out / aw_out (nullable): dL/da and the softmax weights of every row.
+ *   tile_start in tiles of vlsa_mlp_bwd_tile_rows(x_dtype) rows.
+ * vlsa_attn_scores_backward_dx_seeded: vlsa_attn_scores_backward_dx with the seed read from seed_word. */
+int vlsa_gated_scores_batch_train(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated, const int* tile_start,
+                                  int n_tiles, int rows_per_tile, float* a, const int64_t* a_off, int64_t a_floats, float drop_p,
+                                  const int64_t* seed_word, void* stream);
+int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated, const int* tile_start,
+                                  int n_tiles, const float* a_raw, const int64_t* a_off, const float* m2, const float* l, int m_stride,
+                                  const float* pooled, const float* dpooled, void* ws, float* dW, float* dvec, float* da_out,
+                                  float* aw_out, float drop_p, const int64_t* seed_word, void* stream);
+int vlsa_attn_scores_backward_dx_seeded(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
+                                        const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
+                                        const float* aw, const float* dpooled, const int64_t* a_off, float drop_p,
+                                        const int64_t* seed_word, void* stream);
 int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc, int B, int D, const void* qprep, int P, float coattn_scale,
                            const int* tile_start, int n_tiles, const float* dout, const float* out, const float* m2, const float* l,
                            float* delta_ws, void* stream);

@@ -167,6 +167,13 @@ _SIGNATURES = {
     "vlsa_prepare_attn_dx_weights": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "vlsa_attn_scores_backward_dx": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_float, c_uint32, c_void_p]),
+    "vlsa_gated_scores_batch_train": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                              c_int64, c_float, c_void_p, c_void_p]),
+    "vlsa_attn_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_float, c_void_p, c_void_p]),
+    "vlsa_attn_scores_backward_dx_seeded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "vlsa_gated_scores_train": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_float, c_uint32, c_void_p]),
     "vlsa_feat_project_train": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "vlsa_feat_project_rowstats": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

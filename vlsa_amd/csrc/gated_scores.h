@@ -72,6 +72,9 @@ struct GsBatch {
     unsigned int drop_thr, drop_seed;
     float drop_scale;
     unsigned int row_base;      // first row of this launch inside the bag's score array (a bag may be covered by two launches)
+    // batched training forward (vlsa_gated_scores_batch_train): the seed is read from this device word, bag b uses
+    // bag_drop_seed(word, b); null: drop_seed for every row
+    const long long* seed_word;
 };
 
 

@@ -154,9 +154,11 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
     // FULL: 256-row tiles, everything static (large bags); otherwise the row-tile count is a run-time, wave-uniform value
     const int nrt = FULL ? RT : (rows_per_tile >> 4);
     int tile = HALVES == 1 ? bid : bid < nfull ? ((bid >> 4) << 3) + (bid & 7) : bid >> 1;
+    unsigned int drop_seed = bt.drop_seed;
     if (bt.bags != nullptr) {   // one vector load of the (<= 65-entry) tile table + a ballot instead of a dependent scalar search
         const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
         const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= tile)) - 1;
+        if (GATED && bt.seed_word != nullptr) drop_seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
         const GsBag bag = bt.bags[b];
         Xv = bag.X;
         N = bag.N;
@@ -401,8 +403,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
                           : GATED ? gate_act(acc[rt][hg][0][r], acc[rt][hg][NB - 1][r]) : tanh_act(acc[rt][hg][0][r]);
                 if (GATED && bt.drop_thr != 0u) {      // uniform: training-mode dropout on both branches
                     const unsigned int row = rid0 + 16 * rt + 4 * g + r, h = (unsigned int)(h0 + 16 * hg);
-                    const bool ka = dropout_bits(bt.drop_seed, row, h) >= bt.drop_thr;
-                    const bool kg = dropout_bits(bt.drop_seed, row, h + 256u) >= bt.drop_thr;
+                    const bool ka = dropout_bits(drop_seed, row, h) >= bt.drop_thr;
+                    const bool kg = dropout_bits(drop_seed, row, h + 256u) >= bt.drop_thr;
                     e = (ka && kg) ? e * bt.drop_scale * bt.drop_scale : 0.f;
                 }
                 ew += e * w2v[hg];
@@ -658,11 +660,19 @@ extern "C" int vlsa_gated_scores_train(const void* X, int x_dtype, int64_t N, in
 // B bags in ONE launch.  bag_desc: device table of vlsa_bag_desc {X, N, ldx}; tile_start [B + 1] (device, int32): first row tile
 // of every bag for tiles of `rows_per_tile` rows (a multiple of 16, <= 256; <= 128 for gated fp32 bags), n_tiles = tile_start[B];
 // a: one buffer holding all bags' scores, bag b at a + a_off[b] (device, int64), a_floats = its length (zeroed here).
-extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
-                                       const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
-                                       int64_t a_floats, void* stream) {
+static int gated_scores_batch_impl(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
+                                   const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
+                                   int64_t a_floats, float drop_p, const int64_t* seed_word, void* stream) {
     if (!bag_desc || !prep || !a || !tile_start || !a_off || B < 1 || B > 64 || n_tiles < 1 || a_floats < 1) return VLSA_EINVAL;
     if (D != gs::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
+    GsBatch bt{static_cast<const GsBag*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u, nullptr};
+    if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_train; the seed comes from the device word
+        if (!(drop_p < 1.f) || !seed_word) return VLSA_EINVAL;
+        bt.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
+        if (bt.drop_thr == 0u) bt.drop_thr = 1u;
+        bt.drop_scale = 1.f / (1.f - drop_p);
+        bt.seed_word = reinterpret_cast<const long long*>(seed_word);
+    }
     const bool f32 = x_dtype == VLSA_DT_F32;
     const GsTiling tl = gs_tiling(f32, gated != 0, 0);
     const int max_rows = tl.max_rows;
@@ -670,7 +680,6 @@ extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype,
         // tiles higher than the fragment-order kernel's: the persistent LDS-DMA kernel (vlsa_gated_scores_big_tile)
         hipStream_t st = (hipStream_t)stream;
         if (gated && hipMemsetAsync(a, 0, (size_t)a_floats * sizeof(float), st) != hipSuccess) return VLSA_ELAUNCH;
-        const GsBatch bt{static_cast<const GsBag*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u};
         return gs_tile_launch(nullptr, 0ll, 0ll, static_cast<const unsigned char*>(prep), gated, a, n_tiles, rows_per_tile, bt, nullptr, nullptr, st);
     }
     if (rows_per_tile < 16 || rows_per_tile > max_rows || (rows_per_tile % 16)) return VLSA_EINVAL;
@@ -690,7 +699,6 @@ extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype,
     const bool full = rows_per_tile == max_rows;
     const unsigned int tiles = (unsigned int)n_tiles * tl.halves;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    const GsBatch bt{static_cast<const GsBag*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u};
 #define VLSA_GSB(G, F, X32, RTV) hipLaunchKernelGGL((k_gated_scores<G, F, X32, RTV>), dim3(tiles), dim3(512), X32 ? gs::kLds32 : gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt)
     if (f32 && gated && tl.four_waves) {
         if (full) hipLaunchKernelGGL((k_gated_scores<true, true, true, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
@@ -715,6 +723,26 @@ extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype,
     }
 #undef VLSA_GSB
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+}
+
+extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
+                                       const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
+                                       int64_t a_floats, void* stream) {
+    return gated_scores_batch_impl(bag_desc, B, x_dtype, D, prep, gated, tile_start, n_tiles, rows_per_tile, a, a_off, a_floats, 0.f,
+                                   nullptr, stream);
+}
+
+// Training-mode forward of vlsa_gated_scores_batch: the gated module's dropout (probability drop_p behind tanh and behind sigmoid,
+// the dropout_bits masks of vlsa_gated_scores_train) with the seed READ FROM THE DEVICE WORD seed_word (int64, low 32 bits): an
+// in-stream op that advances the word between steps is recorded by a captured graph, a by-value seed would be baked into it.  Bag b
+// of the batch draws its masks under bag_drop_seed(seed, b) (bag 0: the seed itself).  drop_p = 0 or gated = 0: the inference
+// launch (seed_word may then be NULL).
+extern "C" int vlsa_gated_scores_batch_train(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
+                                             const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
+                                             int64_t a_floats, float drop_p, const int64_t* seed_word, void* stream) {
+    if (drop_p < 0.f) return VLSA_EINVAL;
+    return gated_scores_batch_impl(bag_desc, B, x_dtype, D, prep, gated, tile_start, n_tiles, rows_per_tile, a, a_off, a_floats, drop_p,
+                                   seed_word, stream);
 }
 
 // Scores AND attention pooling of a batch of bf16 bags in ONE launch of the persistent LDS-DMA kernel (+ the per-bag fold of its

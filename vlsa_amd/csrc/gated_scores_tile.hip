@@ -168,7 +168,7 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
     const unsigned int lds0 = (unsigned int)(uintptr_t)(lds_void_ptr_t)smem;
 
     // a tile's X source, all of it wave-uniform (SGPRs): the descriptor over its rows, the row pitch, where its scores go
-    struct Src { i32x4t rs; int ldb; float* a; long long row0; int nrows, n0, n1; const unsigned char* x0; };   // n0, n1: 16-row tiles of row half 0 / 1
+    struct Src { i32x4t rs; int ldb; float* a; long long row0; int nrows, n0, n1; const unsigned char* x0; unsigned int seed; };   // n0, n1: 16-row tiles of row half 0 / 1
     const int xr = lane >> 2;
     const int xchunk = ((lane & 3) ^ ((0 - (xr >> 2)) & 3)) << 4;
     // Who stages what: wave w LDS row blocks w and w + 8 and pieces w, w + 8, w + 16, w + 24 of the step's weight block.  (The SIMD's
@@ -182,9 +182,11 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
         long long N = N0, ldx = ldx0;
         float* a = a_out0;
         int tile = t;
+        unsigned int seed = bt.drop_seed;
         if (bt.bags != nullptr) {
             const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
             const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
+            if (GATED && bt.seed_word != nullptr) seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
             const GsBag bag = bt.bags[b];
             Xv = bag.X;
             N = bag.N;
@@ -208,6 +210,7 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
         r.nrows = (int)((N - r.row0) < rows_pt ? (N - r.row0) : rows_pt);
         if (r.nrows < 0) r.nrows = 0;
         r.a = a;
+        r.seed = seed;
         r.ldb = __builtin_amdgcn_readfirstlane((int)(ldx * 2));
         const unsigned long long xaddr = reinterpret_cast<unsigned long long>(Xv) + (unsigned long long)r.row0 * ldx * 2ull;
         r.x0 = reinterpret_cast<const unsigned char*>(xaddr);
@@ -391,8 +394,8 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
                                       : GATED ? gate_act3(acc[rt][j][r], acc[rt][j + 2][r]) : tanh_act3(acc[rt][j][r]);
                             if constexpr (GATED && decltype(with_dropout)::value) {
                                 const unsigned int row = rid0 + 16 * rt + 4 * g + r, h = (unsigned int)(128 * hv + 32 * wn + 16 * j + i16);
-                                const bool ka = dropout_bits(bt.drop_seed, row, h) >= bt.drop_thr;
-                                const bool kg = dropout_bits(bt.drop_seed, row, h + 256u) >= bt.drop_thr;
+                                const bool ka = dropout_bits(cur.seed, row, h) >= bt.drop_thr;
+                                const bool kg = dropout_bits(cur.seed, row, h + 256u) >= bt.drop_thr;
                                 e = (ka && kg) ? e * bt.drop_scale * bt.drop_scale : 0.f;
                             }
                             ew += e * w2v[j];

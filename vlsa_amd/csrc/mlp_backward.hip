@@ -69,12 +69,22 @@ struct MbArgs {
     // gated scores: the training-mode dropout of the forward (vlsa_gated_scores_train), re-evaluated here; drop_thr = 0: off
     unsigned int drop_thr, drop_seed;
     float drop_scale;
+    const long long* seed_word; // non-null: the seed is read from this device word, bag b uses bag_drop_seed(word, b)
+    // POOL (vlsa_attn_pool_backward_batch): rowvec holds the RAW scores a, and da of the softmax pooling pooled_b = sum_n w_n x_n,
+    // w_n = softmax_b(a)_n = exp2(a_n log2(e) - m2[b]) / l[b], is formed in the tile prologue: da_n = w_n (x_n - pooled_b) . dpooled_b
+    const float* m2;            // [B] at stride m_stride (the forward's per-bag max, exp2 domain)
+    const float* l;             // [B] at stride m_stride (the forward's per-bag sum of 2^(a log2(e) - m2))
+    const float* pooled;        // [B][512] the forward's pooled rows
+    const float* dpooled;       // [B][512] dL/dpooled
+    float* da_out;              // nullable: da of every row (at row_off[b])
+    float* aw_out;              // nullable: w_n of every row (at row_off[b])
+    int m_stride;
 };
 
 __device__ __forceinline__ int mb_swz(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
 
-// MODE: mb::kTanh / kGated / kLN.  XF32: fp32 input rows.
-template <int MODE, bool XF32>
+// MODE: mb::kTanh / kGated / kLN.  XF32: fp32 input rows.  POOL (scores only): da from the pooling's backward, see MbArgs.
+template <int MODE, bool XF32, bool POOL = false>
 __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
     using namespace mb;
     constexpr int RT = XF32 ? 2 : 4;             // 16-row tiles per step
@@ -118,13 +128,21 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;          // scores: db, dw2, dc;  projecter: db, dgamma, dbeta
 
     // ---- tile lookup + register staging of a tile's rows -------------------------------------------------------------------
-    struct Tile { const unsigned char* x; const float* dy; const float* rv; long long ldx, lddy; int nrows; unsigned int rid; };
+    struct Tile { const unsigned char* x; const float* dy; const float* rv; long long ldx, lddy; int nrows, b; unsigned int rid, seed; float m2, linv; };
     auto find = [&](int t) -> Tile {
         const int ts = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
         const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
         const MbBag bag = a.bags[b];
         const long long row0 = (long long)(t - a.tile_start[b]) * ROWS;
         Tile r;
+        r.b = b;
+        r.seed = a.seed_word != nullptr ? bag_drop_seed((unsigned int)*a.seed_word, b) : a.drop_seed;
+        r.m2 = 0.f;
+        r.linv = 0.f;
+        if constexpr (POOL) {
+            r.m2 = a.m2[(size_t)b * a.m_stride];
+            r.linv = 1.f / a.l[(size_t)b * a.m_stride];
+        }
         r.ldx = bag.ldx;
         r.rid = (unsigned int)row0;          // row index inside the bag (the dropout counter of the forward)
         r.nrows = (int)((bag.N - row0) < ROWS ? (bag.N - row0) : ROWS);
@@ -196,6 +214,35 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
             const Tile cur = find(t);
             stage_load(cur);
             stage_store();
+            if constexpr (POOL) {
+                // (x_n - pooled_b) . dpooled_b of the tile's rows from the staged registers: bf16 -- a wave holds rows 8 k + w whole
+                // (8 columns per lane); fp32 -- rows 4 k + w / 2, half a row per wave (4 columns per lane), the halves added in the
+                // order of the waves.  Rows past the bag's end come out as -pooled . dpooled; their da is masked below.
+                constexpr int CPL = XF32 ? 4 : 8;
+                const int col0 = XF32 ? CPL * (64 * (w & 1) + lane) : CPL * lane;
+                const float* dpb = a.dpooled + (size_t)cur.b * kD + col0;
+                const float* plb = a.pooled + (size_t)cur.b * kD + col0;
+                float dpv[CPL], cst = 0.f;
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) {
+                    dpv[e] = dpb[e];
+                    cst = fmaf(plb[e], dpv[e], cst);
+                }
+                float_mb* pd = reinterpret_cast<float_mb*>(smem + kExchOff + 32768);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    float d = -cst;
+#pragma unroll
+                    for (int e = 0; e < CPL; ++e) {
+                        float x;
+                        if constexpr (XF32) x = __uint_as_float(st[k][e]);
+                        else x = __uint_as_float((e & 1) ? (st[k][e >> 1] & 0xffff0000u) : (st[k][e >> 1] << 16));
+                        d = fmaf(x, dpv[e], d);
+                    }
+                    d = wave_sum(d);
+                    if (lane == 0) pd[XF32 ? 2 * (4 * k + (w >> 1)) + (w & 1) : 8 * k + w] = d;
+                }
+            }
             __syncthreads();
             // ---- phase 1: recompute the pre-activations of this wave's 16 units for the tile's rows ----------------------
             f32x4 acch[RT];
@@ -240,7 +287,25 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
             f32x4 rv[RT];             // scores: da of the 4 rows
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                if constexpr (MODE != kLN) {
+                if constexpr (POOL) {
+                    const float_mb* pd = reinterpret_cast<const float_mb*>(smem + kExchOff + 32768);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * rt + 4 * g + r;
+                        float dav = 0.f;
+                        if (row < cur.nrows) {
+                            const float dot = XF32 ? pd[2 * row] + pd[2 * row + 1] : pd[row];
+                            const float wn = exp2f(cur.rv[row] * 1.4426950408889634f - cur.m2) * cur.linv;
+                            dav = wn * dot;
+                            if (sl == 0 && w == 0 && i16 == 0) {      // one writer per row: the tile's chunk, slice 0, wave 0
+                                const long long o = (cur.rv - a.rowvec) + row;
+                                if (a.da_out) a.da_out[o] = dav;
+                                if (a.aw_out) a.aw_out[o] = wn;
+                            }
+                        }
+                        rv[rt][r] = dav;
+                    }
+                } else if constexpr (MODE != kLN) {
                     const int row = 16 * rt + 4 * g;
                     if (row + 3 < cur.nrows) {
                         rv[rt] = f32x4{cur.rv[row], cur.rv[row + 1], cur.rv[row + 2], cur.rv[row + 3]};
@@ -303,8 +368,8 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                             float keep = 1.f;
                             if (MODE == kGated && a.drop_thr != 0u) {      // uniform: the forward's dropout masks of both branches
                                 const unsigned int row = cur.rid + 16 * rt + 4 * g + r, hu = 16 * unit + i16;
-                                const bool ka = dropout_bits(a.drop_seed, row, hu) >= a.drop_thr;
-                                const bool kg = dropout_bits(a.drop_seed, row, hu + 256u) >= a.drop_thr;
+                                const bool ka = dropout_bits(cur.seed, row, hu) >= a.drop_thr;
+                                const bool kg = dropout_bits(cur.seed, row, hu + 256u) >= a.drop_thr;
                                 keep = (ka && kg) ? a.drop_scale * a.drop_scale : 0.f;
                             }
                             d = dav * hv * dfac * other[r] * keep;
@@ -435,12 +500,12 @@ int chunks_for(int n_tiles, int nsl) {
     if (n_tiles < C) C = n_tiles;
     return C < 1 ? 1 : C;
 }
-template <int MODE, bool XF32>
+template <int MODE, bool XF32, bool POOL = false>
 int launch(const MbArgs& a, int nsl, hipStream_t st) {
     static DeviceOnce once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)k_mlp_backward<MODE, XF32>, hipFuncAttributeMaxDynamicSharedMemorySize, mb::kLds);
+    if (once.first()) (void)hipFuncSetAttribute((const void*)k_mlp_backward<MODE, XF32, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, mb::kLds);
     const unsigned int grid = 8u * nsl * ((a.C + 7) / 8);
-    hipLaunchKernelGGL((k_mlp_backward<MODE, XF32>), dim3(grid), dim3(512), mb::kLds, st, a);
+    hipLaunchKernelGGL((k_mlp_backward<MODE, XF32, POOL>), dim3(grid), dim3(512), mb::kLds, st, a);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 }  // namespace
@@ -494,6 +559,67 @@ extern "C" int vlsa_attn_scores_backward(const void* bag_desc, int B, int x_dtyp
     const bool f32 = x_dtype == VLSA_DT_F32;
     if (mode == mb::kGated) rc = f32 ? launch<mb::kGated, true>(a, nsl, st) : launch<mb::kGated, false>(a, nsl, st);
     else rc = f32 ? launch<mb::kTanh, true>(a, nsl, st) : launch<mb::kTanh, false>(a, nsl, st);
+    if (rc != VLSA_OK) return rc;
+    const long long tw = (long long)U * 512, tv = 3 * 512;
+    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
+    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tv / 4 + 31) / 32)), dim3(256), 0, st, a.part_v, a.C, tv, dvec);
+    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+}
+
+// Backward of the (gated) attention POOLING of B bags, pooled_b = softmax_b(a) X_b with a the scores above, in one pass over the rows:
+// the tile prologue of k_mlp_backward forms da_n = w_n (x_n - pooled_b) . dpooled_b from the X tile it stages anyway, so no
+// separate pass over the bags computes dL/da.  a_raw: the forward's raw scores (bag b at a_off[b]); m2 / l: the forward's per-bag
+// softmax max (exp2 domain) and sum at stride m_stride; pooled / dpooled [B][512].  Outputs as vlsa_attn_scores_backward, summed
+// over the bags in its fixed-order reduction; da_out / aw_out (nullable): dL/da and the softmax weights of every row, what
+// vlsa_attn_scores_backward_dx(_seeded) takes when the bags carry a gradient.  seed_word: the device word the training forward
+// (vlsa_gated_scores_batch_train) read its seed from (NULL with drop_p = 0).  Three launches: the pass and two reductions.
+extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
+                                             const int* tile_start, int n_tiles, const float* a_raw, const int64_t* a_off,
+                                             const float* m2, const float* l, int m_stride, const float* pooled, const float* dpooled,
+                                             void* ws, float* dW, float* dvec, float* da_out, float* aw_out, float drop_p,
+                                             const int64_t* seed_word, void* stream) {
+    if (!bag_desc || !prep || !tile_start || !a_raw || !a_off || !m2 || !l || !pooled || !dpooled || !ws || !dW || !dvec || B < 1 || B > 64
+        || n_tiles < 1 || m_stride < 1 || drop_p < 0.f)
+        return VLSA_EINVAL;
+    if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
+    const int nsl = gated ? 4 : 2, U = gated ? 512 : 256;
+    const GatedPrepOffsets L(gated ? 1 : 0);
+    const unsigned char* pp = static_cast<const unsigned char*>(prep);
+    MbArgs a{};
+    a.bags = static_cast<const MbBag*>(bag_desc);
+    a.tile_start = tile_start;
+    a.row_off = reinterpret_cast<const long long*>(a_off);
+    a.rowvec = a_raw;
+    a.wpack = pp + L.wpack;
+    a.bias_a = reinterpret_cast<const float*>(pp + L.ba);
+    a.bias_g = reinterpret_cast<const float*>(pp + L.bg);
+    a.vec = reinterpret_cast<const float*>(pp + L.w2);
+    a.B = B;
+    a.n_tiles = n_tiles;
+    a.C = chunks_for(n_tiles, nsl);
+    a.part_w = static_cast<float*>(ws);
+    a.part_v = a.part_w + (size_t)a.C * U * 512;
+    a.drop_thr = 0u;
+    a.drop_scale = 1.f;
+    if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_batch_train
+        if (!(drop_p < 1.f) || !seed_word) return VLSA_EINVAL;
+        a.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
+        if (a.drop_thr == 0u) a.drop_thr = 1u;
+        a.drop_scale = 1.f / (1.f - drop_p);
+        a.seed_word = reinterpret_cast<const long long*>(seed_word);
+    }
+    a.m2 = m2;
+    a.l = l;
+    a.m_stride = m_stride;
+    a.pooled = pooled;
+    a.dpooled = dpooled;
+    a.da_out = da_out;
+    a.aw_out = aw_out;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    const bool f32 = x_dtype == VLSA_DT_F32;
+    if (gated) rc = f32 ? launch<mb::kGated, true, true>(a, nsl, st) : launch<mb::kGated, false, true>(a, nsl, st);
+    else rc = f32 ? launch<mb::kTanh, true, true>(a, nsl, st) : launch<mb::kTanh, false, true>(a, nsl, st);
     if (rc != VLSA_OK) return rc;
     const long long tw = (long long)U * 512, tv = 3 * 512;
     hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
@@ -597,6 +723,7 @@ struct AdxArgs {
     int B, n_tiles;
     unsigned int drop_thr, drop_seed;
     float drop_scale;
+    const long long* seed_word; // non-null: the seed is read from this device word, bag b uses bag_drop_seed(word, b)
 };
 
 template <bool GATED, bool XF32>
@@ -620,6 +747,7 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
     const int nrows = (int)((bag.N - row0) < ROWS ? (bag.N - row0) : ROWS);
     const unsigned char* xsrc = static_cast<const unsigned char*>(bag.X) + row0 * bag.ldx * (XF32 ? 4 : 2);
     const float* dav = a.da + a.row_off[b] + row0;
+    const unsigned int drop_seed = a.seed_word != nullptr ? bag_drop_seed((unsigned int)*a.seed_word, b) : a.drop_seed;
 
     // ---- X tile -> LDS (layout of k_mlp_backward) ------------------------------------------------------------------------------
 #pragma unroll
@@ -716,8 +844,8 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
                     sg = __builtin_amdgcn_rcpf(1.f + v);
                     if (a.drop_thr != 0u) {
                         const unsigned int rid = (unsigned int)(row0 + row);
-                        const bool ka = dropout_bits(a.drop_seed, rid, (unsigned int)hu) >= a.drop_thr;
-                        const bool kg = dropout_bits(a.drop_seed, rid, (unsigned int)hu + 256u) >= a.drop_thr;
+                        const bool ka = dropout_bits(drop_seed, rid, (unsigned int)hu) >= a.drop_thr;
+                        const bool kg = dropout_bits(drop_seed, rid, (unsigned int)hu + 256u) >= a.drop_thr;
                         keep = (ka && kg) ? a.drop_scale * a.drop_scale : 0.f;
                     }
                 }
@@ -810,10 +938,10 @@ extern "C" int vlsa_prepare_attn_dx_weights(const float* Wa, const float* Wg, in
 // dL/dX of the (gated) attention pooling for B bags whose rows carry a gradient (see k_attn_scores_dx).  dx_desc: table of the fp32
 // gradient rows to write; da / aw: dL/da and the softmax weights A_n of all bags' rows (bag b at a_off[b]); dpooled [B][512] (aw
 // and dpooled may both be NULL: scores term only); prep / prep_t: vlsa_prepare_gated_weights / vlsa_prepare_attn_dx_weights.
-extern "C" int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
-                                            const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
-                                            const float* aw, const float* dpooled, const int64_t* a_off, float drop_p, unsigned int seed,
-                                            void* stream) {
+static int attn_scores_backward_dx_impl(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
+                                        const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
+                                        const float* aw, const float* dpooled, const int64_t* a_off, float drop_p, unsigned int seed,
+                                        const int64_t* seed_word, void* stream) {
     if (!bag_desc || !dx_desc || !prep || !prep_t || !tile_start || !da || !a_off || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
     if ((aw == nullptr) != (dpooled == nullptr)) return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
@@ -842,6 +970,7 @@ extern "C" int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx
         if (a.drop_thr == 0u) a.drop_thr = 1u;
         a.drop_seed = seed;
         a.drop_scale = 1.f / (1.f - drop_p);
+        a.seed_word = reinterpret_cast<const long long*>(seed_word);
     }
     hipStream_t st = (hipStream_t)stream;
     static DeviceOnce once;
@@ -857,6 +986,25 @@ extern "C" int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx
     else       { if (f32) VLSA_ADX(false, true); else VLSA_ADX(false, false); }
 #undef VLSA_ADX
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+}
+
+extern "C" int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
+                                            const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
+                                            const float* aw, const float* dpooled, const int64_t* a_off, float drop_p, unsigned int seed,
+                                            void* stream) {
+    return attn_scores_backward_dx_impl(bag_desc, dx_desc, B, x_dtype, D, prep, prep_t, gated, tile_start, n_tiles, da, aw, dpooled, a_off,
+                                        drop_p, seed, nullptr, stream);
+}
+
+// vlsa_attn_scores_backward_dx with the dropout seed read from the device word seed_word (bag b: bag_drop_seed(word, b)), the word
+// vlsa_gated_scores_batch_train read; NULL only with drop_p = 0.
+extern "C" int vlsa_attn_scores_backward_dx_seeded(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
+                                                   const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
+                                                   const float* aw, const float* dpooled, const int64_t* a_off, float drop_p,
+                                                   const int64_t* seed_word, void* stream) {
+    if (gated && drop_p > 0.f && !seed_word) return VLSA_EINVAL;
+    return attn_scores_backward_dx_impl(bag_desc, dx_desc, B, x_dtype, D, prep, prep_t, gated, tile_start, n_tiles, da, aw, dpooled, a_off,
+                                        drop_p, 0u, seed_word, stream);
 }
 
 // The descriptor tables of ONE bag written on the device from by-value arguments (what vlsa_amd.functional._row_tables uploads for a

@@ -69,6 +69,12 @@ __host__ __device__ __forceinline__ unsigned int dropout_bits(unsigned int seed,
     return h;
 }
 
+// Seed of bag b in a batched training launch whose seed word is s: bag 0 keeps s (a batch of one bag draws the masks of the
+// single-bag path under s), every other bag a hashed seed of its own, so that bags of one launch get independent masks.
+__host__ __device__ __forceinline__ unsigned int bag_drop_seed(unsigned int s, int b) {
+    return b == 0 ? s : dropout_bits(s ^ 0x5BD1E995u, (unsigned int)b, 0xFFFFFFFFu);
+}
+
 __device__ __forceinline__ float load_as_float(const float* p) { return *p; }
 __device__ __forceinline__ float load_as_float(const __bf16* p) { return (float)*p; }
 

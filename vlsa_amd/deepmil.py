@@ -405,9 +405,89 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             return (e @ l2.weight.t() + l2.bias).squeeze(-1)
         return VF.attn_scores(H, Hg, la.bias, lg.bias, l2.weight, l2.bias)
 
-    def forward(self, X, ret_with_attn=False):
+    def _dropout_seed_word(self, device) -> torch.Tensor:
+        """The seed of one batched training forward as a device word: a per-module device counter, its base drawn ONCE from torch's CPU
+        generator (``torch.manual_seed`` governs it), advanced in-stream by every call -- eagerly and in a captured graph's replays
+        alike -- and snapshotted, so that the backward of this call reads the seed its forward read."""
+        ctr = self.__dict__.get("_drop_counter")
+        if ctr is None or ctr.device != device:
+            base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            ctr = self._drop_counter = torch.full((1,), base, dtype=torch.int64, device=device)
+        ctr.add_(1)
+        return ctr.clone()
+
+    def _pool_modules(self):
+        sm = self.sigma._modules
+        if isinstance(self.sigma, Gated_Attention_Pooling):
+            f1, sc = sm["fc1"]._modules, sm["score"]._modules
+            return f1["0"], sc["0"], sm["fc2"], f1["2"], sc["2"]
+        at = sm["attention"]._modules
+        return at["0"], None, at["2"], None, None
+
+    def forward_bags(self, bags, ret_with_attn=False, projected=False):
+        """A list of bags (each [1, N_i, C] or [N_i, C]; a ``BagSet`` is taken as checked) through this encoder as a batch:
+        ``torch.cat([self(x) for x in bags])`` up to fp32 rounding, with ``ret_with_attn`` also the per-bag attention as
+        ``forward(x, ret_with_attn=True)`` hands it out (raw scores for Attention_Pooling, softmax weights for the gated module).
+        (Gated) attention pooling with 512 -> 256 hidden units runs as one autograd node per <= 64 bags
+        (VF.attn_pool_bags_autograd: three launches forward, one backward pass + reductions, dropout seeds from a device counter);
+        mean / max pooling as batched launches.  ``projected``: the bags already went through ``feat_proj``."""
+        flat = bags if isinstance(bags, VF.BagSet) else [VF._bag2d(x) for x in bags]
+        if self.feat_proj is not None and not projected:
+            flat = [self.feat_proj(x) for x in flat]          # fp32 [N, 512]; a trainable projecter gets dX from the pooling
+        if len(flat) == 0:
+            raise ValueError("forward_bags needs at least one bag")
+        bag_grad = torch.is_grad_enabled() and any(x.requires_grad for x in flat)
+        uniform = (all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == flat[0].dtype for x in flat)
+                   and flat[0].dtype in (torch.bfloat16, torch.float32))
+        attn = None
+        sg = self.sigma
+        if sg == "mean":
+            if uniform and not bag_grad:
+                f = torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
+            else:
+                f = torch.stack([x.float().mean(dim=0) if (bag_grad or not x.is_cuda) else VF.scored_pool(x, None) for x in flat])
+        elif sg == "max":
+            f = torch.stack([x.float().amax(dim=0) if (bag_grad or not x.is_cuda) else VF.colmax(x) for x in flat])
+        else:
+            gated = isinstance(sg, Gated_Attention_Pooling)
+            lin_a, lin_g, lin_o, drop_a, drop_g = self._pool_modules()
+            if not (uniform and (not gated or drop_a.p == drop_g.p) and lin_a.in_features == 512 and lin_a.out_features == 256):
+                outs = [self.forward(x[None], ret_with_attn=ret_with_attn, _projected=True) for x in flat]     # other widths: per bag
+                if ret_with_attn:
+                    return torch.cat([o[0] for o in outs]), [o[1] for o in outs]
+                return torch.cat(outs)
+            if not hasattr(self, "_fused_scores"):
+                self._fused_scores = VF.FusedAttnScores()
+            w = (lin_a.weight, lin_a.bias, lin_g.weight if gated else None, lin_g.bias if gated else None, lin_o.weight, lin_o.bias)
+            drop_p = float(drop_a.p) if (gated and sg.training and drop_a.p > 0) else 0.0
+            feats, scores = [], []
+            for i in range(0, len(flat), 64):
+                chunk = flat.chunk(i, 64) if isinstance(flat, VF.BagSet) else flat[i:i + 64]
+                seed = self._dropout_seed_word(chunk[0].device) if drop_p else None
+                pooled, a = VF.attn_pool_bags_autograd(chunk, self._fused_scores, *w, drop_p=drop_p, seed_word=seed)
+                feats.append(pooled)
+                if ret_with_attn:
+                    o = 0
+                    for x in chunk:
+                        n = x.shape[0]
+                        scores.append(a[o:o + n])
+                        o += n
+            f = feats[0] if len(feats) == 1 else torch.cat(feats)
+            if ret_with_attn:
+                attn = [(s[None, :] if not gated else F.softmax(s, dim=0)[None, :]).detach() for s in scores]
+        if self.pred_head == "Adapter":
+            logit = self.keep_ratio * f + (1 - self.keep_ratio) * self.visual_adapter(f)
+        else:
+            logit = self.g(f)
+        if ret_with_attn:
+            if attn is None:
+                raise NotImplementedError("ret_with_attn: mean / max pooling has no attention (model/deepmil.py:270-283)")
+            return logit, attn
+        return logit
+
+    def forward(self, X, ret_with_attn=False, _projected=False):
         assert X.shape[0] == 1
-        if self.feat_proj is not None:
+        if self.feat_proj is not None and not _projected:
             X = self.feat_proj(X)
         raw_attn = fused_logit = None
         x_grad = torch.is_grad_enabled() and X.requires_grad   # a trainable Feat_Projecter in front: the pooling must hand dX back

@@ -1464,6 +1464,164 @@ def attn_scores_autograd(X2: torch.Tensor, fused: "FusedAttnScores", Wa, ba, Wg,
     return _AttnScoresFn.apply(X2, fused, Wa, ba, Wg, bg, w2, c, float(drop_p or 0.0), int(seed or 0))
 
 
+class AttnBagsPlan:
+    """Device tables of one chunk of <= 64 bags for the batched DeepMIL training route (vlsa_gated_scores_batch_train,
+    vlsa_attn_pool_backward_batch): the descriptor table, score offsets a_off [B] (int64), the score kernel's tile_start (tiles of
+    ``rpt`` rows) and the backward's (tiles of vlsa_mlp_bwd_tile_rows).  Derived from the descriptor ON THE DEVICE by in-stream ops
+    -- no staging copy, so a plan may also be built inside a graph capture once the descriptor is up.  A ``BagSet`` keeps its plans."""
+
+    def __init__(self, bags, gated: bool, desc: torch.Tensor):
+        lib = nat.load()
+        self.B = B = len(bags)
+        self.sizes = sizes = [int(x.shape[0]) for x in bags]
+        self.f32 = bags[0].dtype == torch.float32
+        self.dt = nat.DT_F32 if self.f32 else nat.DT_BF16
+        self.total = sum(sizes)
+        self.offs = [0]
+        for n in sizes:
+            self.offs.append(self.offs[-1] + n)
+        max_rows, round_tiles = _score_tiling(self.f32, gated)
+        big_rows, big_min = _score_big_tile(self.f32, gated)
+        tiles = lambda r: sum((n + r - 1) // r for n in sizes)   # noqa: E731
+        rpt = max_rows
+        if big_rows and self.total >= big_min:             # a large bf16 batch: the persistent LDS-DMA score kernel (scores only)
+            rpt = big_rows
+            if tiles(rpt) < 256:
+                rpt = max_rows + 32
+                while rpt < big_rows and tiles(rpt) > 256:
+                    rpt += 32
+        elif tiles(max_rows) < round_tiles:
+            rpt = 16
+            while rpt < max_rows and tiles(rpt) > round_tiles:
+                rpt += 16
+        self.rpt = rpt
+        self.tile_rows = tr = int(lib.vlsa_mlp_bwd_tile_rows(self.dt))
+        self.n_tiles_f, self.n_tiles_b = tiles(rpt), tiles(tr)
+        self.desc = desc
+        n = desc[:, 1]
+        self.a_off = (torch.cumsum(n, 0) - n).contiguous()
+        self.ts_f = torch.zeros(B + 1, dtype=torch.int32, device=desc.device)
+        self.ts_f[1:] = torch.cumsum(torch.div(n + (rpt - 1), rpt, rounding_mode="floor"), 0)
+        self.ts_b = torch.zeros(B + 1, dtype=torch.int32, device=desc.device)
+        self.ts_b[1:] = torch.cumsum(torch.div(n + (tr - 1), tr, rounding_mode="floor"), 0)
+
+    @staticmethod
+    def of(bags, gated: bool) -> "AttnBagsPlan":
+        """the plan of a chunk: kept by a ``BagSet``; a plain list of bags (rows that carry a gradient: the projected bags) gets a
+        fresh one, its descriptor staged from the host -- not possible inside a graph capture"""
+        if isinstance(bags, BagSet):
+            plans = bags.__dict__.setdefault("_attn_plans", {})
+            p = plans.get(bool(gated))
+            if p is None:
+                if bags._desc is None and torch.cuda.is_current_stream_capturing():
+                    raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
+                p = plans[bool(gated)] = AttnBagsPlan(bags, gated, bags.desc())
+            return p
+        if torch.cuda.is_current_stream_capturing():
+            raise VlsaNativeError("the batched DeepMIL route captures over a BagSet (bags without a gradient of their own) only")
+        import numpy as np
+        rows = np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in bags], dtype=np.int64).reshape(len(bags), 3)
+        return AttnBagsPlan(bags, gated, torch.from_numpy(rows).to(bags[0].device))
+
+
+class _AttnPoolBagsFn(torch.autograd.Function):
+    """pooled [B, 512] = softmax_b(a) X_b of (Gated_)Attention_Pooling over a chunk of <= 64 bags as ONE autograd node.  Forward: the
+    training-mode score launch over the bag table (vlsa_gated_scores_batch_train, dropout seed read from a device word), the pooling
+    partials and their merge (per-bag softmax max, sum and pooled row kept).  Backward: vlsa_attn_pool_backward_batch -- dL/da formed
+    inside the backward kernel's tile prologue, the parameter gradients summed over the bags in its fixed-order reduction -- and,
+    only when the bags carry a gradient, dX of all bags in one more launch (vlsa_attn_scores_backward_dx_seeded).  Returns (pooled,
+    a); a is not differentiable here."""
+
+    @staticmethod
+    def forward(ctx, plan, prep, prep_t, Wa, ba, Wg, bg, w2, c, drop_p, seed_word, *bag_tensors):
+        lib, s = nat.load(), _stream()
+        dev, B, gated = plan.desc.device, plan.B, Wg is not None
+        a = torch.empty(plan.total, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_gated_scores_batch_train(_p(plan.desc), B, plan.dt, 512, _p(prep), int(gated), _p(plan.ts_f), plan.n_tiles_f,
+                                                    plan.rpt, _p(a), _p(plan.a_off), plan.total, float(drop_p), _p(seed_word), s),
+                  "vlsa_gated_scores_batch_train")
+        G = max(1, min(64, 512 // B))
+        pm = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        pl = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        pacc = torch.empty(B * G, 512, dtype=torch.float32, device=dev)
+        m2 = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        l = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        pooled = torch.empty(B, 512, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_scored_pool_partial_batch(_p(plan.desc), B, plan.dt, 512, _p(a), _p(plan.a_off), G, _p(pm), _p(pl), _p(pacc), s),
+                  "vlsa_scored_pool_partial_batch")
+        st = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, 512, G * nat.P_STRIDE, G * nat.P_STRIDE, G * 512,
+                                  nat.P_STRIDE, nat.P_STRIDE, 512)
+        nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, 1, 512, 1, st, _p(m2), _p(l), _p(pooled), s),
+                  "vlsa_vlfan_merge_batch_strided")
+        ctx.save_for_backward(a, m2, l, pooled, prep, prep_t, seed_word)
+        ctx.plan, ctx.gated, ctx.drop_p = plan, gated, float(drop_p)
+        ctx.shapes = (w2.shape, c.shape)
+        ctx.bag_dtypes = [x.dtype for x in bag_tensors]
+        ctx.bags = bag_tensors                        # the kernels read them through the descriptor table
+        ctx.mark_non_differentiable(a)
+        return pooled, a
+
+    @staticmethod
+    def backward(ctx, dpooled, _da_unused):
+        lib, s = nat.load(), _stream()
+        a, m2, l, pooled, prep, prep_t, seed_word = ctx.saved_tensors
+        plan, gated = ctx.plan, ctx.gated
+        dev, B = a.device, plan.B
+        dp = _f32c(dpooled)
+        need_dx = any(ctx.needs_input_grad[11:])
+        ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(1 if gated else 0, plan.n_tiles_b), dtype=torch.uint8, device=dev)
+        dW = torch.empty(2 if gated else 1, 256, 512, dtype=torch.float32, device=dev)
+        dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
+        da = torch.empty(plan.total, dtype=torch.float32, device=dev) if need_dx else None
+        aw = torch.empty(plan.total, dtype=torch.float32, device=dev) if need_dx else None
+        nat.check(lib.vlsa_attn_pool_backward_batch(_p(plan.desc), B, plan.dt, 512, _p(prep), int(gated), _p(plan.ts_b), plan.n_tiles_b,
+                                                    _p(a), _p(plan.a_off), _p(m2), _p(l), nat.P_STRIDE, _p(pooled), _p(dp), _p(ws), _p(dW),
+                                                    _p(dvec), _p(da), _p(aw), ctx.drop_p, _p(seed_word), s),
+                  "vlsa_attn_pool_backward_batch")
+        dxs = [None] * B
+        if need_dx:
+            dX = torch.empty(plan.total, 512, dtype=torch.float32, device=dev)
+            n = plan.desc[:, 1]
+            dx_desc = torch.stack([plan.a_off * 2048 + dX.data_ptr(), n, torch.full_like(n, 512)], 1).contiguous()   # (in-stream)
+            nat.check(lib.vlsa_attn_scores_backward_dx_seeded(_p(plan.desc), _p(dx_desc), B, plan.dt, 512, _p(prep), _p(prep_t), int(gated),
+                                                              _p(plan.ts_b), plan.n_tiles_b, _p(da), _p(aw), _p(dp), _p(plan.a_off),
+                                                              ctx.drop_p, _p(seed_word), s), "vlsa_attn_scores_backward_dx_seeded")
+            for i in range(B):
+                if ctx.needs_input_grad[11 + i]:
+                    g = dX[plan.offs[i]:plan.offs[i + 1]]
+                    dxs[i] = g if ctx.bag_dtypes[i] == torch.float32 else g.to(ctx.bag_dtypes[i])
+        w2_shape, c_shape = ctx.shapes
+        return (None, None, None, dW[0], dvec[0, :256], dW[1] if gated else None, dvec[0, 256:] if gated else None,
+                dvec[1, :256].reshape(w2_shape), dvec[2, :1].reshape(c_shape), None, None, *dxs)
+
+
+def attn_pool_bags_autograd(bags, fused: "FusedAttnScores", Wa, ba, Wg, bg, w2, c, drop_p: float = 0.0,
+                            seed_word: Optional[torch.Tensor] = None):
+    """(pooled [B, 512] fp32, raw scores a [sum N_i] fp32) of (Gated_)Attention_Pooling over a chunk of 1..64 bags ([N_i, 512], one
+    dtype, not re-checked: a ``BagSet``, or the projected bags of a trainable Feat_Projecter, which then receive their gradient) as
+    ONE autograd node (_AttnPoolBagsFn).  drop_p > 0 (gated only): training-mode dropout with the seed read from ``seed_word`` (a
+    device int64 word; bag b uses bag_drop_seed(seed, b)).  Inside a graph capture the weights are packed inside the capture, so
+    the graph never reads a packed block that a later repack or a dropped cache could free."""
+    B = len(bags)
+    if not (1 <= B <= 64):
+        raise ValueError("1..64 bags per call")
+    gated = Wg is not None
+    drop_p = float(drop_p or 0.0) if gated else 0.0
+    if drop_p and (seed_word is None or not seed_word.is_cuda or seed_word.dtype != torch.int64):
+        raise VlsaNativeError("dropout in the batched route takes its seed from a device int64 word (seed_word)")
+    dev = bags[0].device
+    plan = AttnBagsPlan.of(bags, gated)
+    bag_grad = torch.is_grad_enabled() and any(x.requires_grad for x in bags)
+    if torch.cuda.is_current_stream_capturing():
+        fresh = FusedAttnScores()
+        prep = fresh._packed(dev, Wa, ba, Wg, bg, w2, c)
+        prep_t = fresh.packed_t(dev, Wa, Wg) if bag_grad else None
+    else:
+        prep = fused._packed(dev, Wa, ba, Wg, bg, w2, c)
+        prep_t = fused.packed_t(dev, Wa, Wg) if bag_grad else None
+    return _AttnPoolBagsFn.apply(plan, prep, prep_t, Wa, ba, Wg, bg, w2, c, drop_p, seed_word if drop_p else None, *bags)
+
+
 def mean_pool_bags(bags) -> torch.Tensor:
     """Row means [B, 512] of up to 64 validated [N_i, 512] device bags (one dtype) in two launches (the 'mean' pooling of
     FeatMIL / DeepMIL over a batch: model/deepmil.py:57-58,271-272 per bag)."""

@@ -921,15 +921,33 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
                 text_n = F.normalize(text_features, dim=-1)
                 image_features = F.normalize(enc.forward_bags(bags), dim=-1)
                 return self.logit_scale.exp() * image_features @ text_n.t(), image_features, text_n
+            if isinstance(enc, mil_encoders.DeepMIL) and len(bags) > 0:
+                return self._deepmil_logits(enc.forward_bags(bags), text_features)
             outs = [self.forward(x if x.dim() == 3 else x[None]) for x in bags]
             return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), outs[0][2]
         with torch.no_grad():
             return self._forward_bags_fused(bags, text_features)
 
+    def _deepmil_logits(self, feats, text_features):
+        """cosine logits of a DeepMIL batch's bag vectors [B, C], as the per-bag ``forward`` forms them: both normalisations and the
+        logits as ONE autograd node (the batched training head with P = 1) where it applies, torch ops otherwise"""
+        if (feats.is_cuda and feats.dtype == torch.float32 and feats.shape[1] % 4 == 0 and feats.shape[1] <= 1024 and text_features.is_cuda
+                and text_features.dim() == 2 and 1 <= text_features.shape[0] <= 64 and text_features.shape[1] == feats.shape[1]
+                and self.logit_scale.is_cuda):
+            return VF.head_train(feats.unsqueeze(1).contiguous(), None, None, text_features, self.logit_scale, self._head_tickets)
+        text_n = F.normalize(text_features, dim=-1)
+        image_features = F.normalize(feats.float(), dim=-1)
+        return self.logit_scale.exp() * image_features @ text_n.t(), image_features, text_n
+
     def _forward_bags_attn(self, bags, text_features):
         enc = self.mil_encoder
+        if isinstance(enc, mil_encoders.DeepMIL):
+            # (gated-)attention pooling: the batched route hands back the per-bag attention of forward(x, ret_with_attn=True)
+            with torch.set_grad_enabled(self._needs_grad(text_features)):
+                feats, attn = enc.forward_bags(bags, ret_with_attn=True)
+                return (*self._deepmil_logits(feats, text_features), attn)
         if not isinstance(enc, VLFAN):
-            raise NotImplementedError("ret_with_attn over a list of bags is the VLFAN encoder's output (model/deepmil.py:206-215)")
+            raise NotImplementedError("ret_with_attn over a list of bags is the VLFAN / DeepMIL encoders' output (model/deepmil.py:206-215)")
         grad = self._needs_grad(text_features)
         spec = enc.fused_head_spec()
         flat = [VF._bag2d(x) for x in bags]
