@@ -8,7 +8,10 @@
 // stream never drains.  The evaluation loop of the reference (runner/vlsa_handler.py:315-345) and its 32-bag training
 // step (189-289) process independent bags back to back -- exactly this shape.
 //
-// Per-tile arithmetic, LDS image, exchange and epilogue are those of k_vlfan_partial_dma (vlfan_partial_dma.hip).
+// Per-tile arithmetic, LDS image, exchange and epilogue are those of k_vlfan_partial_dma (vlfan_partial_dma.hip).  The
+// synchronisation differs: counted s_waitcnt vmcnt(N) keeps the next tile's DMA in flight as there, but the two row groups
+// run one raw s_barrier apart, so the two waves of a SIMD alternate between the matrix-heavy and the latency-bound half of
+// an iteration instead of doing the same half at the same time (the tile loop below).
 #include "vlsa_common.h"
 #ifndef VLSA_DMA_NT
 #define VLSA_DMA_NT "nt"      // streaming rows: non-temporal (measurement builds may pass -DVLSA_DMA_NT=\"\")
@@ -41,12 +44,14 @@ __device__ long long vlsa_dbg_batch[64];
         if (blockIdx.x == 3 && threadIdx.x == 0 && k_ < 40) vlsa_dbg_batch[k_] = __builtin_readcyclecounter(); \
         if (blockIdx.x == 3 && threadIdx.x == 0 && (k_ == 1 || k_ == 39)) vlsa_dbg_batch[k_ == 1 ? 62 : 63] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
+// per-phase stamps of own tile 12 of wave (rg, cw = 0) of workgroup 3: row group 0 in [40, 48), row group 1 in [48, 56)
 #define ISTAMP(k, dep)                                                                                                   \
     do {                                                                                                                 \
         if (kown == 12) {                                                                                                 \
             float sink_ = (dep);                                                                                          \
             asm volatile("v_mov_b32 %0, %0" : "+v"(sink_));                                                              \
-            if (blockIdx.x == 3 && threadIdx.x == 0) vlsa_dbg_batch[40 + (k)] = __builtin_readcyclecounter();            \
+            if (blockIdx.x == 3 && (threadIdx.x & 255) == 0)                                                             \
+                vlsa_dbg_batch[40 + 8 * rg + (k)] = __builtin_readcyclecounter();                                        \
         }                                                                                                                \
     } while (0)
 #else
@@ -245,6 +250,13 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
             if (has_scores && sp_q < P) srow = reinterpret_cast<float*>(sp) + (size_t)sp_q * tab_get(bag, 10) + 4 * (lane & 7);
         }
 
+        // Row group 1 runs ONE barrier behind row group 0: between two barriers a SIMD then pairs one group's phase (a) --
+        // tile wait, next DMA, 32 score / norm MFMAs, exchange write -- with the other group's phase (b) -- exchange read,
+        // normalise, exp2, 16 weighted-sum MFMAs -- instead of both waves' MFMAs queueing on its matrix pipe in the same
+        // window and both waves then waiting out the exchange / exp2 chain with the pipe idle.  Every barrier of the loop
+        // still orders the exchange of the group for which it is the (a) -> (b) or (b) -> (a) boundary (each group has its
+        // own exchange area and ring slots); both groups pass 2 niter + 1 barriers per bag and meet again in the epilogue.
+        if (rg == 1 && !(xmode & 2)) VLSA_BAR();
         for (int it = 0; it < niter; ++it) {
             const int tile = 2 * it + rg;
             const bool have = tile < ntiles;  // wave-uniform
@@ -257,6 +269,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 S[h] = f32x4{0.f, 0.f, 0.f, 0.f};
                 Nd[h] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
+            if (!(xmode & 2)) VLSA_BAR();  // (b) -> (a): this group's readers of its previous exchange are done
             if (have) {
                 int nb, nt;
                 next_of(bag, tile, ntiles, nb, nt);
@@ -294,8 +307,6 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 ISTAMP(2, S[0][0] + S[1][0] + Nd[0][0] + Nd[1][0]);
             }
 
-            if (!(xmode & 2)) VLSA_BAR();  // readers of the previous exchange are done
-            if (have) ISTAMP(3, 0.f);
             {
                 unsigned char* mine = exch + cw * kExchWave;
                 *reinterpret_cast<f32x4_ma*>(mine + (0 * 64 + lane) * 16) = S[0];
@@ -308,7 +319,8 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                     reinterpret_cast<float_ma*>(mine + 2048)[16 + i16] = d1;
                 }
             }
-            if (!(xmode & 2)) VLSA_BAR();
+            if (have) ISTAMP(3, 0.f);
+            if (!(xmode & 2)) VLSA_BAR();  // (a) -> (b): this group's exchange is written
             if (have) {
                 ISTAMP(4, 0.f);
                 f32x4 T[2], R2[2];
@@ -398,6 +410,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
             }
             BSTAMP(stamp++);
         }
+        if (rg == 0 && !(xmode & 2)) VLSA_BAR();  // row group 1's first barrier of the bag (above)
         k0 += (ntiles + 1) >> 1;
         k1 += ntiles >> 1;
 
