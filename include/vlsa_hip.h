@@ -671,6 +671,24 @@ int vlsa_feat_project_rowstats(const float* dy, int64_t lddy, const float* y, in
 int vlsa_feat_project_backward(const void* bag_desc, const void* dy_desc, int B, int x_dtype, const void* prep, const int* tile_start,
                                int n_tiles, const float* stats, const int64_t* row_off, void* ws, float* dW, float* dvec,
                                void* stream);
+/*
+ * Feat_Projecter over a TABLE of B <= 64 bags (an optimizer step's bags) in one launch each way.
+ * vlsa_feat_project_batch: bag_desc = device table of vlsa_bag_desc (bf16 or fp32 rows, N >= 1, 16-byte aligned rows, D == 512);
+ *   tile_start [B + 1] int32 (device): first row tile of every bag in tiles of tile_rows rows, n_tiles = tile_start[B]; tile_rows:
+ *   32, 64 or (bf16 only) 128 -- vlsa_feat_project_batch_tile_rows(x_dtype, total rows of the launch) applies the thresholds the
+ *   single-bag entry points apply to one bag.  Y: PACKED fp32 [sum N][512], bag b at row row_off[b] (int64, device); stats: NULL
+ *   (inference) or [sum N][4] with columns 0, 1 as vlsa_feat_project_train writes them.  A row's result equals the single-bag
+ *   kernel's bit for bit, whatever the tile height and the row's place in its tile.
+ *   VLSA_EINVAL: a NULL pointer, B outside [1, 64], n_tiles < 1, another tile_rows; VLSA_EUNSUPPORTED: D != 512, another dtype.
+ * vlsa_feat_project_rowstats_batch: columns 2, 3 of the packed stats from the packed rows y and the upstream gradient, which arrives
+ *   as one fp32 matrix per bag: dy_desc = device table {pointer, N, row stride >= 512}.  vlsa_feat_project_backward then takes the
+ *   same tables with B > 1.
+ */
+int vlsa_feat_project_batch_tile_rows(int x_dtype, int64_t total_rows);
+int vlsa_feat_project_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, float eps, const int* tile_start,
+                            int n_tiles, int tile_rows, float* Y, const int64_t* row_off, float* stats, void* stream);
+int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, const float* y, const int64_t* row_off, int64_t total_rows,
+                                     const void* prep, float* stats, void* stream);
 /* dL/dX of the (gated) attention pooling over the patches, for bags that carry a gradient (a trainable Feat_Projecter feeding a
  * DeepMIL encoder, model/deepmil.py:267-283): dx_n = dHa_n Wa + dHg_n Wg + A_n dpooled.  prep_t: the un-scaled weights packed
  * [hidden][column] by vlsa_prepare_attn_dx_weights (vlsa_attn_dx_prep_bytes); da / aw: dL/da and the softmax weights of all bags'

@@ -90,17 +90,18 @@ __device__ __forceinline__ float fp_row16_sum(float v) {
     return v;
 }
 
+// One tile of 16 RT rows of ONE bag, rows [row0, row0 + 16 RT) of X [N, ldx], by the whole workgroup (512 threads): the body of both
+// kernels below.  Y / stats are the bag's own (row 0 of the bag first).  A row's arithmetic -- K steps, bias start, the two
+// LayerNorm passes, the fixed-order sum over the eight waves -- depends neither on RT nor on the row's place in the tile.
 template <bool XF32, int RT>
-__global__ __launch_bounds__(512) void k_feat_proj(const void* __restrict__ Xv, long long N, long long ldx,
-                                                    const unsigned char* __restrict__ prep, float eps, float* __restrict__ Y,
-                                                    long long ldy, float* __restrict__ stats) {
+__device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const void* __restrict__ Xv, long long N, long long ldx,
+                                        long long row0, const unsigned char* __restrict__ prep, float eps, float* __restrict__ Y,
+                                        long long ldy, float* __restrict__ stats) {
     using namespace fp;
     constexpr int ROWS = 16 * RT;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i16 = lane & 15;
-    const long long row0 = (long long)blockIdx.x * ROWS;
     const int nrows = (int)((N - row0) < ROWS ? (N - row0) : ROWS);
     const FeatProjLayout L;
 
@@ -286,6 +287,38 @@ __global__ __launch_bounds__(512) void k_feat_proj(const void* __restrict__ Xv, 
     }
 }
 
+template <bool XF32, int RT>
+__global__ __launch_bounds__(512) void k_feat_proj(const void* __restrict__ Xv, long long N, long long ldx,
+                                                    const unsigned char* __restrict__ prep, float eps, float* __restrict__ Y,
+                                                    long long ldy, float* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    fp_tile<XF32, RT>(smem, Xv, N, ldx, (long long)blockIdx.x * (16 * RT), prep, eps, Y, ldy, stats);
+}
+
+struct FpBag {                 // vlsa_bag_desc
+    const void* X;
+    long long N, ldx;
+};
+
+// The same tile for a TABLE of B <= 64 bags in one launch: workgroup t finds its bag from tile_start [B + 1] (tiles of 16 RT rows,
+// counted bag by bag) as the multi-bag kernels of mlp_backward.hip do, and writes to the packed output Y [sum N][512] / stats
+// [sum N][4], bag b at row row_off[b].  Everything that selects the rows is wave-uniform (scalar loads).
+template <bool XF32, int RT>
+__global__ __launch_bounds__(512) void k_feat_proj_bags(const FpBag* __restrict__ bags, int B, const int* __restrict__ tile_start,
+                                                         const long long* __restrict__ row_off, const unsigned char* __restrict__ prep,
+                                                         float eps, float* __restrict__ Y, float* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, t = blockIdx.x;
+    const int ts = lane < B ? tile_start[lane] : 0x7fffffff;
+    const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1);
+    if (b < 0) return;
+    const FpBag bag = bags[b];
+    const long long row0 = (long long)(t - tile_start[b]) * (16 * RT);
+    if (row0 >= bag.N) return;              // (a table that does not match the grid: nothing is read or written)
+    const long long off = row_off[b];
+    fp_tile<XF32, RT>(smem, bag.X, bag.N, bag.ldx, row0, prep, eps, Y + off * fp::kD, fp::kD, stats != nullptr ? stats + off * 4 : nullptr);
+}
+
 }  // namespace vlsa
 
 using namespace vlsa;
@@ -301,6 +334,14 @@ extern "C" int vlsa_prepare_featproj(const float* W, const float* b, const float
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 
+// rows per workgroup for a launch over N rows: every workgroup streams the whole 1 MB of packed weights from L2, so the largest tile
+// (bf16 128, fp32 64 rows) that still leaves >= 120 workgroups, else 32 rows (10k-patch bag: 79 tiles of 128 rows 33.7 us, 157 of
+// 64 27 us, 313 of 32 30-35 us; tools/kbench_featproj.py)
+static int fp_tile_rows(bool f32, int64_t N) {
+    if (!f32 && N >= 120 * 128) return 128;
+    return N >= 120 * 64 ? 64 : 32;
+}
+
 static int feat_project_impl(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const void* prep, float eps, float* Y,
                              int64_t ldy, float* stats, void* stream) {
     if (!X || !prep || !Y || N < 1 || ldx < D || ldy < D) return VLSA_EINVAL;
@@ -310,18 +351,16 @@ static int feat_project_impl(const void* X, int x_dtype, int64_t N, int64_t ldx,
     if ((reinterpret_cast<uintptr_t>(X) & 15) || ((ldx * esz) % 16)) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    // rows per workgroup: every workgroup streams the whole 1 MB of packed weights from L2, so the largest tile (bf16 128, fp32
-    // 64 rows) that still leaves >= 120 workgroups, else 32 rows (10k-patch bag: 79 tiles of 128 rows 33.7 us, 157 of 64 27 us,
-    // 313 of 32 30-35 us; tools/kbench_featproj.py)
 #define VLSA_FP(X32, RT_)                                                                                                  \
     hipLaunchKernelGGL((k_feat_proj<X32, RT_>), dim3((unsigned int)((N + 16 * RT_ - 1) / (16 * RT_))), dim3(512), fp::kLds, st, X, \
                        (long long)N, (long long)ldx, pp, eps, Y, (long long)ldy, stats)
+    const int rows = fp_tile_rows(f32, N);
     if (f32) {
-        if (N >= 120 * 64) VLSA_FP(true, 4);
+        if (rows == 64) VLSA_FP(true, 4);
         else VLSA_FP(true, 2);
     } else {
-        if (N >= 120 * 128) VLSA_FP(false, 8);
-        else if (N >= 120 * 64) VLSA_FP(false, 4);
+        if (rows == 128) VLSA_FP(false, 8);
+        else if (rows == 64) VLSA_FP(false, 4);
         else VLSA_FP(false, 2);
     }
 #undef VLSA_FP
@@ -339,4 +378,41 @@ extern "C" int vlsa_feat_project_train(const void* X, int x_dtype, int64_t N, in
                                        int64_t ldy, float* stats, void* stream) {
     if (!stats) return VLSA_EINVAL;
     return feat_project_impl(X, x_dtype, N, ldx, D, prep, eps, Y, ldy, stats, stream);
+}
+
+// Rows per tile of vlsa_feat_project_batch for a launch over total_rows rows (all bags together): the thresholds the single-bag
+// entry points apply to one bag.  32, 64 or (bf16) 128; 0 for a dtype the kernel does not take.
+extern "C" int vlsa_feat_project_batch_tile_rows(int x_dtype, int64_t total_rows) {
+    if (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32) return 0;
+    return fp_tile_rows(x_dtype == VLSA_DT_F32, total_rows);
+}
+
+// Feat_Projecter over B <= 64 bags in ONE launch.  bag_desc: device table of vlsa_bag_desc {X, N >= 1, ldx} (rows 16-byte aligned,
+// as vlsa_feat_project asks); tile_start [B + 1] (device, int32): first tile of every bag in tiles of tile_rows rows, n_tiles =
+// tile_start[B]; tile_rows: 32, 64 or (bf16) 128 -- vlsa_feat_project_batch_tile_rows picks it from the launch's total row count.
+// Y: packed fp32 [sum N][512], bag b at row row_off[b] (device int64); stats: NULL (inference) or [sum N][4], columns 0, 1 written
+// as by vlsa_feat_project_train.  Every row equals, bit for bit, what the single-bag entry points give for it.
+extern "C" int vlsa_feat_project_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, float eps, const int* tile_start,
+                                       int n_tiles, int tile_rows, float* Y, const int64_t* row_off, float* stats, void* stream) {
+    if (!bag_desc || !prep || !tile_start || !Y || !row_off || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
+    if (D != fp::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
+    const bool f32 = x_dtype == VLSA_DT_F32;
+    if (tile_rows != 32 && tile_rows != 64 && !(tile_rows == 128 && !f32)) return VLSA_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* pp = static_cast<const unsigned char*>(prep);
+    const FpBag* bags = static_cast<const FpBag*>(bag_desc);
+    const long long* ro = reinterpret_cast<const long long*>(row_off);
+#define VLSA_FPB(X32, RT_)                                                                                                        \
+    hipLaunchKernelGGL((k_feat_proj_bags<X32, RT_>), dim3((unsigned int)n_tiles), dim3(512), fp::kLds, st, bags, B, tile_start, ro, pp, \
+                       eps, Y, stats)
+    if (f32) {
+        if (tile_rows == 64) VLSA_FPB(true, 4);
+        else VLSA_FPB(true, 2);
+    } else {
+        if (tile_rows == 128) VLSA_FPB(false, 8);
+        else if (tile_rows == 64) VLSA_FPB(false, 4);
+        else VLSA_FPB(false, 2);
+    }
+#undef VLSA_FPB
+    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }

@@ -449,18 +449,14 @@ __global__ __launch_bounds__(256) void k_mb_reduce(const float* __restrict__ par
 
 // Per-row LayerNorm-backward scalars of the projecter (one wave per row): c1 = mean_o(dy gamma), c2 = mean_o(dy (y - beta))
 // [= mean_o(dy gamma zhat): no division by gamma], written behind the forward's (mean, rstd) into stats[row][2..3].
-__global__ __launch_bounds__(256) void k_ln_bwd_rowstats(const float* __restrict__ dy, long long lddy, const float* __restrict__ y,
-                                                          long long ldy, long long N, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float* __restrict__ stats) {
-    const int lane = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= N) return;
+__device__ __forceinline__ void ln_bwd_row(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, float* __restrict__ st, int lane) {
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int col = 4 * lane + 256 * k;
-        const f32x4 d = *reinterpret_cast<const f32x4*>(dy + row * lddy + col);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(y + row * ldy + col);
+        const f32x4 d = *reinterpret_cast<const f32x4*>(dy + col);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(y + col);
         const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + col);
         const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + col);
 #pragma unroll
@@ -472,9 +468,36 @@ __global__ __launch_bounds__(256) void k_ln_bwd_rowstats(const float* __restrict
     s1 = wave_sum(s1);
     s2 = wave_sum(s2);
     if (lane == 0) {
-        stats[row * 4 + 2] = s1 * (1.f / 512.f);
-        stats[row * 4 + 3] = s2 * (1.f / 512.f);
+        st[2] = s1 * (1.f / 512.f);
+        st[3] = s2 * (1.f / 512.f);
     }
+}
+
+__global__ __launch_bounds__(256) void k_ln_bwd_rowstats(const float* __restrict__ dy, long long lddy, const float* __restrict__ y,
+                                                          long long ldy, long long N, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    ln_bwd_row(dy + row * lddy, y + row * ldy, gamma, beta, stats + row * 4, lane);
+}
+
+// The same over the packed rows of B <= 64 bags (y [total][512], stats [total][4], bag b at row row_off[b]) whose gradient rows
+// arrive as one matrix per bag: dyb [B] = {pointer, N, row stride}.
+__global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const MbBag* __restrict__ dyb, int B, const long long* __restrict__ row_off,
+                                                               const float* __restrict__ y, long long total,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= total) return;
+    const long long ro = lane < B ? row_off[lane] : 0x7fffffffffffffffll;
+    const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ro <= row)) - 1);
+    if (b < 0) return;
+    const MbBag g = dyb[b];
+    const long long r = row - row_off[b];
+    if (r >= g.N) return;                     // (a table that does not cover the row: nothing is read)
+    ln_bwd_row(static_cast<const float*>(g.X) + r * g.ldx, y + row * 512, gamma, beta, stats + row * 4, lane);
 }
 
 }  // namespace vlsa
@@ -637,6 +660,20 @@ extern "C" int vlsa_feat_project_rowstats(const float* dy, int64_t lddy, const f
     hipLaunchKernelGGL(k_ln_bwd_rowstats, dim3((unsigned int)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, (long long)lddy, y,
                        (long long)ldy, (long long)N, reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta),
                        stats);
+    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+}
+
+// The same for the packed rows of B <= 64 bags in one launch: y [total_rows][512] and stats [total_rows][4] hold bag b at row
+// row_off[b] (device int64, ascending from 0: what vlsa_feat_project_batch wrote), dy_desc is the device table {ptr, N, ld} of the
+// per-bag gradient rows (fp32, ld >= 512, 16-byte aligned rows).
+extern "C" int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, const float* y, const int64_t* row_off, int64_t total_rows,
+                                                const void* prep, float* stats, void* stream) {
+    if (!dy_desc || !y || !row_off || !prep || !stats || B < 1 || B > 64 || total_rows < 1) return VLSA_EINVAL;
+    const FeatProjOffsets L;
+    const unsigned char* pp = static_cast<const unsigned char*>(prep);
+    hipLaunchKernelGGL(k_ln_bwd_rowstats_bags, dim3((unsigned int)((total_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const MbBag*>(dy_desc), B, reinterpret_cast<const long long*>(row_off), y, (long long)total_rows,
+                       reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta), stats);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 

@@ -284,9 +284,9 @@ class VLFAN(VF.nat.TransientCaches, nn.Module):
         ``(A, pool_scores)`` when the query pooling is a module (model/deepmil.py:206-215).  ``projected``: the bags already
         went through ``project``."""
         if self.feat_proj is not None and not projected:
-            # one fused HIP launch per bag, fp32 out; a projecter that trains records its LayerNorm statistics and receives its
-            # gradient from the HIP backward kernels (the aggregation hands dX back for the projected bags)
-            bags = [self.feat_proj(x) for x in bags]
+            # one fused HIP launch per chunk of 64 bags, fp32 out; a projecter that trains records its LayerNorm statistics and
+            # receives its gradient from the HIP backward kernels (the aggregation hands dX back for the projected bags)
+            bags = self.feat_proj.forward_bags(bags)
         outs_cat, attn = self._aggregate_bags(bags, ret_with_attn)
         pooled_out, pooled_ext = self.forward_query_pooling(outs_cat)
         feats = self.visual_adapter(pooled_out)
@@ -301,7 +301,7 @@ class VLFAN(VF.nat.TransientCaches, nn.Module):
         and backward) -- ``forward_bags`` without the query pooling and the adapter.  A trainable Feat_Projecter is part of
         the graph (HIP forward + backward; the aggregation hands dX back for the projected fp32 bags)."""
         if self.feat_proj is not None:
-            bags = [self.feat_proj(x) for x in bags]
+            bags = self.feat_proj.forward_bags(bags)
         return self._aggregate_bags(bags, False)[0]
 
     def _aggregate_bags(self, bags, ret_with_attn):
@@ -433,7 +433,7 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
         mean / max pooling as batched launches.  ``projected``: the bags already went through ``feat_proj``."""
         flat = bags if isinstance(bags, VF.BagSet) else [VF._bag2d(x) for x in bags]
         if self.feat_proj is not None and not projected:
-            flat = [self.feat_proj(x) for x in flat]          # fp32 [N, 512]; a trainable projecter gets dX from the pooling
+            flat = self.feat_proj.forward_bags(flat)          # fp32 [N, 512]; a trainable projecter gets dX from the pooling
         if len(flat) == 0:
             raise ValueError("forward_bags needs at least one bag")
         bag_grad = torch.is_grad_enabled() and any(x.requires_grad for x in flat)
@@ -462,7 +462,7 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             drop_p = float(drop_a.p) if (gated and sg.training and drop_a.p > 0) else 0.0
             feats, scores = [], []
             for i in range(0, len(flat), 64):
-                chunk = flat.chunk(i, 64) if isinstance(flat, VF.BagSet) else flat[i:i + 64]
+                chunk = flat.chunk(i, 64) if isinstance(flat, VF.BagSet) else (flat if len(flat) <= 64 else flat[i:i + 64])
                 seed = self._dropout_seed_word(chunk[0].device) if drop_p else None
                 pooled, a = VF.attn_pool_bags_autograd(chunk, self._fused_scores, *w, drop_p=drop_p, seed_word=seed)
                 feats.append(pooled)

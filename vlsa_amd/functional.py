@@ -657,7 +657,8 @@ def _vlfan_dx(bags, qbuf, P: int, scale: float, dout: torch.Tensor, out: torch.T
         if x.dtype != torch.float32 or x.shape[1] != 512:
             raise VlsaNativeError("the HIP aggregation produces dX for fp32 bags with D == 512 only (the output of a trainable "
                                   "Feat_Projecter); detach the bag or use such a bag")
-    dxs = [torch.empty(x.shape[0], 512, dtype=torch.float32, device=dev) for x in bags]
+    # one packed buffer, views handed out: the projecter's backward (_FeatProjectBagsFn) then receives rows that are already contiguous
+    dxs = list(torch.empty(sum(x.shape[0] for x in bags), 512, dtype=torch.float32, device=dev).split([x.shape[0] for x in bags]))
     B = len(bags)
     keep, p_desc, p_dx, _, p_ts, n_tiles, _ = _row_tables(bags, 64, extra=dxs)
     delta = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
@@ -1517,6 +1518,9 @@ class AttnBagsPlan:
                     raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
                 p = plans[bool(gated)] = AttnBagsPlan(bags, gated, bags.desc())
             return p
+        desc = bags.desc() if isinstance(bags, ProjectedBags) else None
+        if desc is not None:                    # a BagSet's bags behind a Feat_Projecter: table derived on the device
+            return AttnBagsPlan(bags, gated, desc)
         if torch.cuda.is_current_stream_capturing():
             raise VlsaNativeError("the batched DeepMIL route captures over a BagSet (bags without a gradient of their own) only")
         import numpy as np
@@ -1675,6 +1679,10 @@ class FusedFeatProjecter:
         _no_bag_grad(X2)
         return _FeatProjectFn.apply(X2, self, W, b, gamma, beta, eps)
 
+    def forward_bags(self, bags, W, b, gamma, beta, eps: float) -> list:
+        """A chunk of 1..64 bags in ONE launch, see ``feat_project_bags``."""
+        return feat_project_bags(bags, self, W, b, gamma, beta, eps)
+
     def __call__(self, X2: torch.Tensor, W, b, gamma, beta, eps: float) -> torch.Tensor:
         lib = nat.load()
         X2 = _bag2d(X2)
@@ -1722,6 +1730,155 @@ class _FeatProjectFn(torch.autograd.Function):
                                                  _p(dvec), s), "vlsa_feat_project_backward")
         hb, hg, hbt = ctx.has
         return None, None, dW, dvec[0] if hb else None, dvec[1] if hg else None, dvec[2] if hbt else None, None
+
+
+class FeatProjBagsPlan:
+    """Tables of one chunk of <= 64 bags for the batched Feat_Projecter (vlsa_feat_project_batch, vlsa_feat_project_rowstats_batch,
+    vlsa_feat_project_backward with B bags): the descriptor table, the row offsets of the packed output and tile_start for the forward
+    (tiles of ``rt`` rows, chosen from the chunk's TOTAL row count) -- for a plain list ONE upload (_row_tables); for a ``BagSet``
+    derived from its descriptor on the device by in-stream ops and kept with the set (nothing is staged per call, so the call can
+    also run inside a graph capture), together with the backward's tile_start."""
+
+    def __init__(self, bags):
+        lib = nat.load()
+        is_set = isinstance(bags, BagSet)
+        self.bags, self.B = bags, len(bags)
+        self.sizes = [int(n) for n in (bags.sizes if is_set else [x.shape[0] for x in bags])]
+        self.dt = bags.dt if is_set else _dt(bags[0])
+        self.total = sum(self.sizes)
+        self.offs = [0]
+        for n in self.sizes:
+            self.offs.append(self.offs[-1] + n)
+        self.rt = rt = int(lib.vlsa_feat_project_batch_tile_rows(self.dt, self.total))
+        self.tr = tr = int(lib.vlsa_mlp_bwd_tile_rows(self.dt))
+        self.n_tiles_b = sum((n + tr - 1) // tr for n in self.sizes)
+        self.on_device = is_set
+        if is_set:
+            if bags._desc is None and torch.cuda.is_current_stream_capturing():
+                raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
+            desc = bags.desc()
+            n = desc[:, 1]
+            self.n_rows = n
+            self.row_off = (torch.cumsum(n, 0) - n).contiguous()
+            ts_f = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
+            ts_f[1:] = torch.cumsum(torch.div(n + (rt - 1), rt, rounding_mode="floor"), 0)
+            self.ts_b = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
+            self.ts_b[1:] = torch.cumsum(torch.div(n + (tr - 1), tr, rounding_mode="floor"), 0)
+            self.keep = (desc, ts_f)
+            self.p_desc, self.p_off, self.p_ts = desc.data_ptr(), self.row_off.data_ptr(), ts_f.data_ptr()
+            self.n_tiles = sum((n + rt - 1) // rt for n in self.sizes)
+        else:
+            if self.B > 1 and torch.cuda.is_current_stream_capturing():
+                raise VlsaNativeError("the batched Feat_Projecter captures over a BagSet only (its tables are derived on the device)")
+            self.keep, self.p_desc, _, self.p_off, self.p_ts, self.n_tiles, _ = _row_tables(bags, rt)
+
+    @staticmethod
+    def of(bags) -> "FeatProjBagsPlan":
+        if isinstance(bags, BagSet):
+            p = bags.__dict__.get("_featproj_plan")
+            if p is None:
+                p = bags.__dict__["_featproj_plan"] = FeatProjBagsPlan(bags)
+            return p
+        return FeatProjBagsPlan(bags)
+
+
+class ProjectedBags(list):
+    """The projected bags of one chunk: the per-bag fp32 [N_i, 512] views of ONE packed allocation.  When the chunk came from a
+    ``BagSet`` their descriptor table is derived on the device (``desc``), so the batched DeepMIL pooling behind a projecter needs no
+    staging copy either -- and can run inside a graph capture."""
+
+    def __init__(self, views, plan: FeatProjBagsPlan):
+        super().__init__(views)
+        self.plan, self._desc = plan, None
+
+    def desc(self) -> Optional[torch.Tensor]:
+        p = self.plan
+        if not p.on_device:
+            return None
+        if self._desc is None:
+            self._desc = torch.stack([p.row_off * 2048 + self[0].data_ptr(), p.n_rows, torch.full_like(p.n_rows, 512)], 1).contiguous()
+        return self._desc
+
+
+def _feat_project_bags_launch(plan: FeatProjBagsPlan, prep: torch.Tensor, eps: float, train: bool):
+    """packed Y [sum N_i, 512] (and stats [sum N_i, 4] when training) of a chunk: ONE allocation each, ONE launch"""
+    lib, dev = nat.load(), prep.device
+    Y = torch.empty(plan.total, 512, dtype=torch.float32, device=dev)
+    stats = torch.empty(plan.total, 4, dtype=torch.float32, device=dev) if train else None
+    nat.check(lib.vlsa_feat_project_batch(plan.p_desc, plan.B, plan.dt, 512, _p(prep), float(eps), plan.p_ts, plan.n_tiles, plan.rt, _p(Y),
+                                          plan.p_off, _p(stats), _stream()), "vlsa_feat_project_batch")
+    return Y, stats
+
+
+class _FeatProjectBagsFn(torch.autograd.Function):
+    """Feat_Projecter over a chunk of <= 64 bags as ONE autograd node: forward = one launch into the packed Y (the outputs are its
+    per-bag views) that also stores the LayerNorm statistics; backward = the per-bag gradients the downstream nodes hand back (views
+    of one packed buffer when they come from _vlfan_dx / the DeepMIL pooling backward), one row-statistics launch over the packed
+    rows, one vlsa_feat_project_backward with B bags: one dW / dvec, summed over the bags in the kernel's fixed-order reduction.
+    The bags themselves carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, plan, prep, W, b, gamma, beta, eps):
+        Y, stats = _feat_project_bags_launch(plan, prep, eps, True)
+        ctx.save_for_backward(Y, stats, prep)
+        ctx.plan = plan
+        ctx.has = (b is not None, gamma is not None, beta is not None)
+        return tuple(Y.split(plan.sizes))
+
+    @staticmethod
+    def backward(ctx, *dys):
+        lib, s = nat.load(), _stream()
+        Y, stats, prep = ctx.saved_tensors
+        plan = ctx.plan
+        dev, B = Y.device, plan.B
+        grads = []
+        for g, n in zip(dys, plan.sizes):
+            g = torch.zeros(n, 512, dtype=torch.float32, device=dev) if g is None else _f32c(g).reshape(n, 512)
+            grads.append(g if g.data_ptr() % 16 == 0 else g.clone())
+        if plan.on_device:
+            # a BagSet: nothing is staged -- the gradient table is derived on the device from the packed rows (the downstream nodes
+            # hand out views of one buffer; anything else is packed first)
+            base = grads[0].data_ptr()
+            if any(g.data_ptr() != base + 2048 * o for g, o in zip(grads, plan.offs)):
+                packed = torch.cat(grads)
+                grads, base = [packed], packed.data_ptr()
+            dy_desc = torch.stack([plan.row_off * 2048 + base, plan.n_rows, torch.full_like(plan.n_rows, 512)], 1).contiguous()
+            p_desc, p_dy, p_off, p_ts, n_tiles = plan.p_desc, dy_desc.data_ptr(), plan.p_off, plan.ts_b.data_ptr(), plan.n_tiles_b
+        else:
+            keep, p_desc, p_dy, p_off, p_ts, n_tiles, _ = _row_tables(plan.bags, plan.tr, extra=grads)
+        nat.check(lib.vlsa_feat_project_rowstats_batch(p_dy, B, _p(Y), p_off, plan.total, _p(prep), _p(stats), s),
+                  "vlsa_feat_project_rowstats_batch")
+        ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(2, n_tiles), dtype=torch.uint8, device=dev)
+        dW = torch.empty(512, 512, dtype=torch.float32, device=dev)
+        dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_feat_project_backward(p_desc, p_dy, B, plan.dt, _p(prep), p_ts, n_tiles, _p(stats), p_off, _p(ws), _p(dW),
+                                                 _p(dvec), s), "vlsa_feat_project_backward")
+        hb, hg, hbt = ctx.has
+        return None, None, dW, dvec[0] if hb else None, dvec[1] if hg else None, dvec[2] if hbt else None, None
+
+
+def feat_project_bags(bags, fused: "FusedFeatProjecter", W, b, gamma, beta, eps: float) -> list:
+    """Feat_Projecter (Linear(512, 512) + LayerNorm, model/layers.py:65-82) over a chunk of 1..64 bags -- [N_i, 512] device tensors of
+    one dtype (bf16 or fp32) with N_i >= 1 and 16-byte aligned rows, not re-checked (``Feat_Projecter.forward_bags`` checks), or a
+    ``BagSet`` -- in ONE launch: returns the per-bag fp32 [N_i, 512] views of one packed allocation (``ProjectedBags``), each row
+    bit-equal to what the per-bag kernel gives.  With grad enabled and a trainable parameter the chunk is ONE autograd node
+    (_FeatProjectBagsFn).  Inside
+    a graph capture the weights are packed inside the capture, so a replay never reads a packed block that a later repack or a
+    dropped cache could free."""
+    B = len(bags)
+    if not (1 <= B <= 64):
+        raise ValueError("1..64 bags per call")
+    _need_gpu(bags[0])
+    dev = bags[0].device
+    if torch.cuda.is_current_stream_capturing():
+        fused = FusedFeatProjecter()
+    prep = fused.packed(dev, W, b, gamma, beta)
+    plan = FeatProjBagsPlan.of(bags)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (W, b, gamma, beta)):
+        _no_bag_grad(*bags)
+        return ProjectedBags(_FeatProjectBagsFn.apply(plan, prep, W, b, gamma, beta, float(eps)), plan)
+    Y, _ = _feat_project_bags_launch(plan, prep, eps, False)
+    return ProjectedBags(Y.split(plan.sizes), plan)
 
 
 def topk_mean(S: torch.Tensor, k: int, out_scale: float = 1.0) -> torch.Tensor:

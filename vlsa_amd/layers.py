@@ -60,6 +60,34 @@ class Feat_Projecter(_TransientCaches, nn.Module):
             return self.projecter(x.reshape(-1, d)).reshape(b, n, -1)
         return self.projecter(x)
 
+    def forward_bags(self, bags):
+        """``[self(x) for x in bags]`` for a list (or ``BagSet``) of bags, each [N_i, 512] or [1, N_i, 512]: ONE fused HIP launch per
+        chunk of 64 bags into one packed fp32 allocation (vlsa_feat_project_batch; the results are its per-bag views, bit-equal to
+        the per-bag kernel's) and, when the projecter trains, ONE autograd node per chunk whose backward sums dW over the bags in
+        one kernel.  Anything the batch kernel does not take -- CPU tensors, widths other than 512, no affine LayerNorm, a bag that
+        itself requires grad, mixed dtypes, an empty bag -- goes bag by bag through ``forward``."""
+        from . import functional as VF
+        lin, norm = self.projecter[0], self.projecter[1]
+        is_set = isinstance(bags, VF.BagSet)
+        grad = torch.is_grad_enabled()
+
+        def takes(x):
+            return (x.is_cuda and (x.dim() == 2 or (x.dim() == 3 and x.shape[0] == 1)) and x.shape[-1] == 512 and x.shape[-2] > 0
+                    and x.dtype == bags[0].dtype and x.device == bags[0].device and not (grad and x.requires_grad))
+        if not (len(bags) > 0 and lin.in_features == 512 and lin.out_features == 512 and tuple(norm.normalized_shape) == (512,)
+                and norm.elementwise_affine and lin.weight.is_cuda and bags[0].dtype in (torch.bfloat16, torch.float32)
+                and ((is_set and bags.D == 512) or all(takes(x) for x in bags))):
+            return [self.forward(x) for x in bags]
+        if not hasattr(self, "_fused"):
+            self._fused = VF.FusedFeatProjecter()
+        if is_set and len(bags) <= 64:          # one chunk of a BagSet: the packed views with their device-side table, as they are
+            return self._fused.forward_bags(bags, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps)
+        out = []
+        for i in range(0, len(bags), 64):
+            chunk = bags.chunk(i, 64) if is_set else [VF._bag2d(x) for x in bags[i:i + 64]]
+            out.extend(self._fused.forward_bags(chunk, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps))
+        return out if is_set else [y if x.dim() == 2 else y[None] for x, y in zip(bags, out)]
+
 
 def _note(module, x):
     """the pooling modules' own ``forward`` is plain torch: meant for the P query rows inside VLFAN; ``DeepMIL`` drives the fused

@@ -974,7 +974,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         projected = False
         if (getattr(enc, "feat_proj", None) is not None and isinstance(enc, (VLFAN, mil_encoders.DeepMIL)) and len(flat) > 0
                 and all(x.is_cuda and x.shape[0] > 0 for x in flat)):
-            flat = [enc.feat_proj(x) for x in flat]    # use_feat_proj=True: one fused HIP launch per bag, fp32 [N, 512] out
+            flat = enc.feat_proj.forward_bags(flat)    # use_feat_proj=True: one fused HIP launch per 64 bags, fp32 [N, 512] out
             projected = True
         ok = (spec is not None and spec[0] != "module" and len(flat) > 0
               and ((trusted and not projected)
