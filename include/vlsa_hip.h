@@ -725,6 +725,40 @@ int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc, int B, int
                            const int* tile_start, int n_tiles, const float* dout, const float* out, const float* m2, const float* l,
                            float* delta_ws, void* stream);
 
+/* ---- DSMIL (model/deepmil.py:638-721) over a table of bags -------------------------------------------------------------------
+ * The dual-stream MIL baseline collapsed to two streaming passes with the C class rows as queries (csrc/dsmil.hip): instance
+ * scores c = X Wc^T + bc are never stored, only each class's maximum and its row (EQUAL maxima resolve to the lowest row index; the
+ * reference's torch.sort leaves ties open); q(.) runs on the C critical rows only; A = softmax_n(x_n . u_k) with
+ * u_k = Wq^T qmax_k / sqrt(H) weights the un-normalised rows; B = Wv z + bv, logits = 0.5 (fcc(B) + cmax).  All products are fp32 FMA.
+ *   bag_desc   device table of B vlsa_bag_desc (1 <= B <= 64, bf16 or fp32 rows, one dtype).  D == 512, H == 256, 1 <= C <= 16:
+ *              VLSA_EUNSUPPORTED otherwise.
+ *   part_start [B + 1] int32 (device): bag b owns the partial records part_start[b] .. part_start[b + 1], vlsa_dsmil_parts(N_b) of
+ *              them -- a function of N_b alone, so a bag's result does not depend on the batch it travels in; n_parts = part_start[B].
+ *   Wc [C][512], bc [C]  i_classifier.fc.0;  Wq [256][512], bq [256]  b_classifier.q;  Wv, bv  b_classifier.v.1;
+ *   Wf [C][C][256], bf [C]  b_classifier.fcc (Conv1d(C, C, kernel_size = 256)).
+ *   drop_p     b_classifier.v.0 in training mode: the value side sees x_n[f] * keep(seed_b, n, f) / (1 - drop_p) with the counter-
+ *              based bits of the attention-score kernels (row = the row's index in its bag, unit = the feature index f), seed_b =
+ *              bag_drop_seed(low 32 bits of *seed_word, b).  0: evaluation, seed_word may be NULL.
+ *   ws         scratch of vlsa_dsmil_workspace_bytes(n_parts, C); nothing in it outlives a call.
+ *   state      vlsa_dsmil_state_floats(B, C, offsets9) floats the backward reads; offsets9 (nullable) receives the float offsets of
+ *              crit [B][16] (int32 critical row per class), cmax [B][16], m2 [B][16] (softmax maximum, exp2 domain), l [B][16],
+ *              xcrit [B][C][512], qmax [B][C][256], u [B][C][512], z [B][C][512], bm [B][C][256] (= B of the reference).
+ *   logits     [B][C];  attn (nullable): mean_k A[n,k] of every row, bag b at attn + a_off[b] (int64, device) -- one more pass.
+ * vlsa_dsmil_backward_batch: the parameter gradients of sum_b dlogits[b] . logits[b], summed over the bags in bag order
+ * (bit-reproducible): one streaming pass that recomputes A from (m2, l) and regenerates the masks, and three small launches.  The bag
+ * rows receive no gradient.  Same drop_p / seed_word contents as the forward it belongs to. */
+int vlsa_dsmil_parts(int64_t N);
+size_t vlsa_dsmil_workspace_bytes(int n_parts, int C);
+size_t vlsa_dsmil_state_floats(int B, int C, int64_t* offsets9);
+int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int C, const int* part_start, int n_parts,
+                             const float* Wc, const float* bc, const float* Wq, const float* bq, const float* Wv, const float* bv,
+                             const float* Wf, const float* bf, float drop_p, const int64_t* seed_word, void* ws, float* state,
+                             float* logits, float* attn, const int64_t* a_off, void* stream);
+int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int C, const int* part_start, int n_parts,
+                              const float* Wq, const float* Wv, const float* Wf, const float* dlogits, float drop_p,
+                              const int64_t* seed_word, const float* state, void* ws, float* dWc, float* dbc, float* dWq, float* dbq,
+                              float* dWv, float* dbv, float* dWf, float* dbf, void* stream);
+
 /* Device-side descriptor tables of ONE bag for the *_backward entry points above (bag_desc [1], optional second table, row
  * offset [1], tile_start [2]) written from by-value arguments by a one-thread kernel: dst = 64 bytes of device memory.  Returns the
  * number of tiles (> 0) or a negative error code.  Layout: {X, N, ld} {extra, N, extra_ld}? {0} {int32 0, int32 n_tiles}. */

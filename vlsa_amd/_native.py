@@ -185,6 +185,13 @@ _SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p]),
     "vlsa_vlfan_backward_dx": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vlsa_dsmil_parts": (c_int, [c_int64]),
+    "vlsa_dsmil_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vlsa_dsmil_state_floats": (c_size_t, [c_int, c_int, c_void_p]),
+    "vlsa_dsmil_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 8
+                                 + [c_float] + [c_void_p] * 7),
+    "vlsa_dsmil_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4
+                                  + [c_float] + [c_void_p] * 12),
     "vlsa_debug_probe": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),
     "vlsa_xchg_max_peers": (c_int, []),
     "vlsa_xchg_result_floats": (c_size_t, [c_int, c_int, c_int, c_void_p]),

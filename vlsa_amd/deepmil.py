@@ -4,6 +4,7 @@ classes (same constructor kwargs, attribute names and state-dict keys), with the
     VLFAN         model/deepmil.py:74-215     language-guided cross-attention aggregation (the shipped encoder)
     FeatMIL       model/deepmil.py:40-67      mean / max / identity (zero-shot)
     DeepMIL       model/deepmil.py:222-292    ABMIL-style (gated-)attention pooling over the N patches
+    DSMIL         model/deepmil.py:638-721    dual-stream MIL (instance max + critical-instance attention), an SA baseline
     logit_pooling model/deepmil.py:16-37      top-k / mean pooling of per-patch class logits
 
 The reference picks the encoder with ``getattr(model.deepmil, cfg['name'])(**cfg)`` (model/utils_vl.py:129-138);
@@ -20,7 +21,7 @@ import torch.nn.functional as F
 from . import functional as VF
 from .layers import Adapter, Attention_Pooling, Feat_Projecter, Gated_Attention_Pooling
 
-__all__ = ["logit_pooling", "FeatMIL", "VLFAN", "DeepMIL"]
+__all__ = ["logit_pooling", "FeatMIL", "VLFAN", "DeepMIL", "DSMIL"]
 
 
 _LOGIT_POOLINGS = {"logit_mean": None, "logit_max": 1}
@@ -556,3 +557,106 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
         if ret_with_attn:
             return logit, raw_attn.detach()
         return logit
+
+
+class _FCLayer(nn.Module):
+    """model/deepmil.py:638-644: holds ``fc.0`` (the instance classifier).  Parameters only: DSMIL.forward drives the kernels."""
+
+    def __init__(self, in_size, out_size=1):
+        super().__init__()
+        self.fc = nn.Sequential(nn.Linear(in_size, out_size))
+
+
+class _BClassifier(nn.Module):
+    """model/deepmil.py:661-671: holds ``q``, ``v.0`` (dropout) / ``v.1`` and ``fcc``.  Parameters only."""
+
+    def __init__(self, input_size, hid_size, output_class, dropout_v=0.0):
+        super().__init__()
+        self.q = nn.Linear(input_size, hid_size)
+        self.v = nn.Sequential(nn.Dropout(dropout_v), nn.Linear(input_size, hid_size))
+        self.fcc = nn.Conv1d(output_class, output_class, kernel_size=hid_size)
+
+
+class DSMIL(VF.nat.TransientCaches, nn.Module):
+    """DSMIL (Li et al., CVPR 2021; model/deepmil.py:692-721) with the reference's constructor and state-dict keys
+    (``i_classifier.fc.0.*``, ``b_classifier.q.*``, ``b_classifier.v.1.*``, ``b_classifier.fcc.*``, ``feat_proj.*``).
+
+    The reference projects all N rows through ``q`` and ``v``; here the module runs as two streaming passes over the bag with the
+    ``num_cls`` class rows as queries (csrc/dsmil.hip: instance maxima, critical rows, online-softmax aggregation, head), forward
+    and backward in HIP, for ``dim_in = 512``, ``dim_hid = 256``, ``num_cls <= 16``.  Gradients reach the eight DSMIL parameters;
+    the bag rows get none, so a ``Feat_Projecter`` in front must be frozen while DSMIL trains.  Equal instance scores resolve to the
+    lowest row index (the reference's ``torch.sort`` leaves ties open)."""
+
+    _transient = {}
+
+    def __init__(self, dim_in=1024, dim_hid=256, num_cls=2, use_feat_proj=True, drop_rate=0.25, **kwargs):
+        super().__init__()
+        self.feat_proj = Feat_Projecter(dim_in, dim_in) if use_feat_proj else None
+        self.i_classifier = _FCLayer(in_size=dim_in, out_size=num_cls)
+        self.b_classifier = _BClassifier(dim_in, dim_hid, num_cls, dropout_v=drop_rate)
+
+    _dropout_seed_word = DeepMIL._dropout_seed_word
+
+    def _weights(self):
+        bc = self.b_classifier._modules
+        fc = self.i_classifier._modules["fc"]._modules["0"]
+        q, v, fcc = bc["q"], bc["v"]._modules["1"], bc["fcc"]
+        return fc.weight, fc.bias, q.weight, q.bias, v.weight, v.bias, fcc.weight, fcc.bias
+
+    def forward_bags(self, bags, ret_with_attn=False, projected=False, ret_critical=False):
+        """A list of bags (each [1, N_i, 512] or [N_i, 512]; a ``BagSet`` is taken as checked) as batches of <= 64 per launch chain:
+        ``torch.cat([self(x) for x in bags])`` bit for bit.  Returns logits [B, C]; with ``ret_with_attn`` also the list of per-bag
+        attention [1, N_i] (``A.mean(dim=1)`` of the reference); with ``ret_critical`` also the critical rows [B, C] (int32)."""
+        Wc, bcl, Wq, bq, Wv, bv, Wf, bf = w = self._weights()
+        if Wc.shape[1] != 512 or Wq.shape[0] != 256 or not (1 <= Wc.shape[0] <= 16):
+            raise VF.VlsaNativeError(f"DSMIL: the HIP kernels cover dim_in = 512, dim_hid = 256, num_cls <= 16 (got {Wc.shape[1]}, "
+                                     f"{Wq.shape[0]}, {Wc.shape[0]}); there is no other route")
+        grad = torch.is_grad_enabled()
+        is_set = isinstance(bags, VF.BagSet)
+        if not is_set:
+            if len(bags) == 0:
+                raise ValueError("forward_bags needs at least one bag")
+            VF._need_gpu(*bags)
+            bags = [VF._bag2d(x) for x in bags]
+        if grad and any(x.requires_grad for x in bags):
+            raise VF.VlsaNativeError("DSMIL: the bag requires grad, but the HIP backward produces parameter gradients only (no dX)")
+        if self.feat_proj is not None and not projected:
+            if grad and any(p.requires_grad for p in self.feat_proj.parameters()):
+                raise VF.VlsaNativeError("DSMIL: a trainable Feat_Projecter needs the gradient of the bag rows, which the DSMIL backward does "
+                                         "not produce; freeze feat_proj (requires_grad_(False)) or run under torch.no_grad()")
+        if not is_set and not all(x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == bags[0].dtype and x.device == bags[0].device
+                                  for x in bags):
+            raise VF.VlsaNativeError("DSMIL takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device")
+        drop = self.b_classifier._modules["v"]._modules["0"]
+        drop_p = float(drop.p) if (self.training and drop.p > 0) else 0.0
+        logits, attn, crit = [], [], []
+        for i in range(0, len(bags), 64):
+            chunk = bags.chunk(i, 64) if is_set else (bags if len(bags) <= 64 else bags[i:i + 64])
+            if self.feat_proj is not None and not projected:
+                chunk = self.feat_proj.forward_bags(chunk)
+                if not isinstance(chunk, VF.ProjectedBags):
+                    chunk = [VF._bag2d(x) for x in chunk]
+            seed = self._dropout_seed_word(chunk[0].device) if drop_p else None
+            lg, a, cr = VF.dsmil_bags(chunk, *w, drop_p=drop_p, seed_word=seed, want_attn=ret_with_attn)
+            logits.append(lg)
+            crit.append(cr)
+            if ret_with_attn:
+                attn.extend(t[None, :] for t in a.split([int(x.shape[0]) for x in chunk]))
+        out = (logits[0] if len(logits) == 1 else torch.cat(logits),)
+        if ret_with_attn:
+            out += (attn,)
+        if ret_critical:
+            out += (crit[0] if len(crit) == 1 else torch.cat(crit),)
+        return out[0] if len(out) == 1 else out
+
+    def forward(self, X, **kwargs):
+        assert X.shape[0] == 1
+        ret_attn = bool(kwargs.get("ret_with_attn"))
+        ret_crit = bool(kwargs.get("ret_critical"))
+        res = self.forward_bags([X], ret_with_attn=ret_attn, ret_critical=ret_crit)
+        if not (ret_attn or ret_crit):
+            return res
+        res = list(res)
+        if ret_attn:
+            res[1] = res[1][0]
+        return tuple(res)

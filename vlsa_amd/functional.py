@@ -2107,3 +2107,113 @@ def query_pool_attention(rows: torch.Tensor, module) -> Tuple[torch.Tensor, torc
                                             _p(_f32c(l2.weight).reshape(-1)), _p(_f32c(l2.bias).reshape(-1)), hid, int(not gated),
                                             _p(ws), _p(pooled), _p(scores), _stream()), "vlsa_query_pool_attention")
     return pooled, scores
+
+
+# ---- DSMIL (model/deepmil.py:638-721): the dual-stream baseline as two streaming passes over a table of bags ---------------------
+class DsmilBagsPlan:
+    """Device tables of one chunk of <= 64 bags for vlsa_dsmil_forward_batch / _backward_batch: the descriptor table, part_start
+    [B + 1] (bag b owns vlsa_dsmil_parts(N_b) partial records -- a function of N_b alone, so a bag's result is the same in any
+    batch) and the attention offsets a_off.  Derived from the descriptor ON THE DEVICE by in-stream ops, so a plan may be built
+    inside a graph capture once the descriptor is up.  A ``BagSet`` keeps its plan."""
+
+    def __init__(self, bags, desc: torch.Tensor):
+        lib = nat.load()
+        self.B = len(bags)
+        self.sizes = [int(x.shape[0]) for x in bags]
+        self.dt = nat.DT_F32 if bags[0].dtype == torch.float32 else nat.DT_BF16
+        self.total = sum(self.sizes)
+        self.n_parts = sum(int(lib.vlsa_dsmil_parts(n)) for n in self.sizes)
+        self.desc = desc
+        n = desc[:, 1]
+        self.a_off = (torch.cumsum(n, 0) - n).contiguous()
+        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
+        self.part_start[1:] = torch.cumsum(torch.clamp(torch.div(n + 511, 512, rounding_mode="floor"), 1, 64), 0)   # vlsa_dsmil_parts
+
+    @staticmethod
+    def of(bags) -> "DsmilBagsPlan":
+        if isinstance(bags, BagSet):
+            p = bags.__dict__.get("_dsmil_plan")
+            if p is None:
+                if bags._desc is None and torch.cuda.is_current_stream_capturing():
+                    raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
+                p = bags.__dict__["_dsmil_plan"] = DsmilBagsPlan(bags, bags.desc())
+            return p
+        desc = bags.desc() if isinstance(bags, ProjectedBags) else None
+        if desc is not None:
+            return DsmilBagsPlan(bags, desc)
+        if torch.cuda.is_current_stream_capturing():
+            raise VlsaNativeError("the batched DSMIL route captures over a BagSet only (its tables are derived on the device)")
+        import numpy as np
+        rows = np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in bags], dtype=np.int64).reshape(len(bags), 3)
+        return DsmilBagsPlan(bags, torch.from_numpy(rows).to(bags[0].device))
+
+
+def dsmil_state_views(state: torch.Tensor, B: int, C: int) -> dict:
+    """the named pieces of a vlsa_dsmil_forward_batch state block (see include/vlsa_hip.h)"""
+    off = (ctypes.c_int64 * 9)()
+    total = int(nat.load().vlsa_dsmil_state_floats(B, C, off))
+    o = list(off) + [total]
+    names = ("crit", "cmax", "m2", "l", "xcrit", "qmax", "u", "z", "bm")
+    shapes = ((B, 16), (B, 16), (B, 16), (B, 16), (B, C, 512), (B, C, 256), (B, C, 512), (B, C, 512), (B, C, 256))
+    out = {k: state[o[i]:o[i + 1]].view(*sh) for i, (k, sh) in enumerate(zip(names, shapes))}
+    out["crit"] = out["crit"].view(torch.int32)
+    return out
+
+
+class _DsmilBagsFn(torch.autograd.Function):
+    """logits [B, C] (and mean_k A[n,k] of every row) of DSMIL over a chunk of <= 64 bags as ONE autograd node: four launches forward
+    (a fifth with the attention), four backward; gradients for the eight parameters, none for the bag rows."""
+
+    @staticmethod
+    def forward(ctx, plan, drop_p, seed_word, want_attn, Wc, bc, Wq, bq, Wv, bv, Wf, bf, *bag_tensors):
+        lib, s = nat.load(), _stream()
+        dev, B, C = plan.desc.device, plan.B, Wc.shape[0]
+        w = [_f32c(t) for t in (Wc, bc, Wq, bq, Wv, bv, Wf, bf)]
+        ws = torch.empty(lib.vlsa_dsmil_workspace_bytes(plan.n_parts, C), dtype=torch.uint8, device=dev)
+        state = torch.empty(lib.vlsa_dsmil_state_floats(B, C, None), dtype=torch.float32, device=dev)
+        logits = torch.empty(B, C, dtype=torch.float32, device=dev)
+        attn = torch.empty(plan.total, dtype=torch.float32, device=dev) if want_attn else None
+        nat.check(lib.vlsa_dsmil_forward_batch(_p(plan.desc), B, plan.dt, Wc.shape[1], Wq.shape[0], C, _p(plan.part_start), plan.n_parts,
+                                               *[_p(t) for t in w], float(drop_p), _p(seed_word), _p(ws), _p(state), _p(logits), _p(attn),
+                                               _p(plan.a_off), s), "vlsa_dsmil_forward_batch")
+        ctx.save_for_backward(state, seed_word, w[2], w[4], w[6])
+        ctx.plan, ctx.drop_p, ctx.C = plan, float(drop_p), C
+        ctx.shapes = [t.shape for t in (Wc, bc, Wq, bq, Wv, bv, Wf, bf)]
+        ctx.bags = bag_tensors                        # the kernels read them through the descriptor table
+        if attn is None:
+            attn = logits.new_empty(0)
+        crit = dsmil_state_views(state, B, C)["crit"][:, :C].clone()
+        ctx.mark_non_differentiable(attn, crit)
+        return logits, attn, crit
+
+    @staticmethod
+    def backward(ctx, dlogits, _dattn, _dcrit):
+        lib, s = nat.load(), _stream()
+        state, seed_word, Wq, Wv, Wf = ctx.saved_tensors
+        plan, C = ctx.plan, ctx.C
+        dev, B = state.device, plan.B
+        g = _f32c(dlogits)
+        ws = torch.empty(lib.vlsa_dsmil_workspace_bytes(plan.n_parts, C), dtype=torch.uint8, device=dev)
+        grads = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes]
+        nat.check(lib.vlsa_dsmil_backward_batch(_p(plan.desc), B, plan.dt, 512, 256, C, _p(plan.part_start), plan.n_parts, _p(Wq), _p(Wv),
+                                                _p(Wf), _p(g), ctx.drop_p, _p(seed_word), _p(state), _p(ws), *[_p(t) for t in grads], s),
+                  "vlsa_dsmil_backward_batch")
+        return (None, None, None, None, *grads, *([None] * len(ctx.bags)))
+
+
+def dsmil_bags(bags, Wc, bc, Wq, bq, Wv, bv, Wf, bf, drop_p: float = 0.0, seed_word: Optional[torch.Tensor] = None,
+               want_attn: bool = False):
+    """DSMIL over a chunk of 1..64 bags ([N_i, 512], one dtype, N_i >= 1, not re-checked: a ``BagSet``, projected bags or validated
+    tensors): (logits [B, C], attention [sum N_i] or None, critical rows [B, C] int32), differentiable w.r.t. the eight parameters.  drop_p > 0: training-mode
+    dropout on the value side, the seed read from ``seed_word`` (device int64; bag b uses bag_drop_seed(seed, b))."""
+    B = len(bags)
+    if not (1 <= B <= 64):
+        raise ValueError("1..64 bags per call")
+    _need_gpu(bags[0], Wc)
+    _no_bag_grad(*bags)
+    drop_p = float(drop_p or 0.0)
+    if drop_p and (seed_word is None or not seed_word.is_cuda or seed_word.dtype != torch.int64):
+        raise VlsaNativeError("DSMIL's dropout takes its seed from a device int64 word (seed_word)")
+    plan = DsmilBagsPlan.of(bags)
+    logits, attn, crit = _DsmilBagsFn.apply(plan, drop_p, seed_word if drop_p else None, bool(want_attn), Wc, bc, Wq, bq, Wv, bv, Wf, bf, *bags)
+    return logits, (attn if want_attn else None), crit

@@ -4,6 +4,8 @@ model/prompt_learners/__init__.py:6-24): what ``VLSAHandler.func_load_model`` re
 
     load_model('VLSA', text_encoder_cfg=..., image_encoder_cfg=..., prompt_learner_cfg=..., pretrained_prompt_learner_cfg=...,
                vlsa_api=..., path_clip_model=...)  ->  vlsa_amd.vlsa.VLSA
+    load_model('DeepMIL', [512, 256, 4], network='ABMIL' | 'MaxMIL' | 'MeanMIL' | 'DSMIL', ...)  ->  vlsa_amd.deepmil.DeepMIL / DSMIL
+               (what ``SAHandler.func_load_model`` reaches, runner/sa_handler.py)
 
 ``patch_reference()`` is the one-line swap for a process running the reference's code: it points the reference's factory
 (and its MIL-encoder name lookup) at the classes of this package, after which ``runner/vlsa_handler.py`` runs unmodified --
@@ -17,14 +19,38 @@ __all__ = ["load_model", "Deep_VLSA", "get_prompt_encoder", "load_prompt_learner
            "arch_cfg_from_run_cfg", "func_load_model"]
 
 
+_MISSING_DEPENDENCY = {"TransMIL": "nystrom_attention (NystromAttention)", "ILRA": "nystrom_attention (via model/deepmil.py's imports)",
+                       "DeepAttnMISL": "the per-slide cluster labels of its dataset pipeline", "PatchGCN": "torch_geometric"}
+
+
 def load_model(arch: str, dims: Optional[List] = None, **kws):
-    """model/utils.py:13-38.  Only the 'VLSA' arch is this package's business; the plain MIL baselines
-    (``arch='DeepMIL'``: ABMIL / TransMIL / DSMIL ... classifiers of sa_handler) are out of scope."""
+    """model/utils.py:13-36.  ``'VLSA'`` builds the language-guided model; ``'DeepMIL'`` builds the survival baselines of
+    ``runner/sa_handler.py`` that have HIP kernels here -- ``network='ABMIL' | 'MaxMIL' | 'MeanMIL'`` (``vlsa_amd.deepmil.DeepMIL``,
+    with the reference's ``pooling`` assertions) and ``'DSMIL'`` (``vlsa_amd.deepmil.DSMIL``) -- from ``dims = [dim_in, dim_hid,
+    num_cls]``.  DSMIL's backward reaches its own eight parameters, not the bag rows: with ``use_feat_proj=True`` (the constructor's
+    default; every shipped cfg_sa_base_conch.yaml sets False) freeze ``model.feat_proj`` before training, or the first step raises.
+    TransMIL / ILRA / DeepAttnMISL / PatchGCN are not served: NotImplementedError names what they would need."""
     if arch == "VLSA":
         return Deep_VLSA(**kws)
     if arch == "DeepMIL":
-        raise NotImplementedError("arch='DeepMIL' (the non-VL survival baselines of model/utils.py:14-33) is outside the "
-                                  "language-guided aggregation path this package implements; use the reference's own factory")
+        assert "network" in kws, "Please specify a network for a DeepMIL arch."
+        network = kws["network"]
+        from .deepmil import DSMIL, DeepMIL
+        if network == "ABMIL":                      # model/utils.py:72-77
+            if "pooling" in kws:
+                assert kws["pooling"] in ["attention", "gated_attention"]
+            return DeepMIL(dims[0], dims[1], dims[2], **kws)
+        if network in ("MaxMIL", "MeanMIL"):        # model/utils.py:79-91
+            pooling = "max" if network == "MaxMIL" else "mean"
+            if "pooling" in kws:
+                assert kws["pooling"] == pooling
+            return DeepMIL(dims[0], dims[1], dims[2], **dict(kws, pooling=pooling))
+        if network == "DSMIL":                      # model/utils.py:67-70
+            return DSMIL(dims[0], dims[1], dims[2], **kws)
+        if network in _MISSING_DEPENDENCY:
+            raise NotImplementedError(f"network={network!r} has no HIP implementation in this package (the reference's needs "
+                                      f"{_MISSING_DEPENDENCY[network]}); use the reference's own factory for it")
+        raise NotImplementedError(f"DeepMIL network {network!r} cannot be recognized")
     raise NotImplementedError("Backbone {} cannot be recognized".format(arch))
 
 
@@ -61,6 +87,9 @@ def load_prompt_adapter(prompt_encoder, cfg: dict):
     """model/prompt_learners/__init__.py:20-24"""
     from .prompt_adapter import PromptAdapter
     return PromptAdapter(prompt_encoder, **cfg)
+
+
+_ABSENT = object()      # patch_reference: the patched module did not have the attribute
 
 
 def _sub_cfg(cfg: dict, prefix: str) -> dict:
@@ -123,6 +152,9 @@ def patch_reference(resident_bags: bool = False, defer_training_calls: bool = Tr
       model from the handler's unmodified ``arch_cfg``;
     * ``model.deepmil.{VLFAN, FeatMIL, DeepMIL, logit_pooling}`` -> this package's: the name lookup of
       model/utils_vl.py:129-138 and ``utils/model_inference.py`` see the same classes.
+    * ``model.utils.DeepMIL``, ``model.utils.DSMIL`` and ``model.deepmil.DSMIL`` -> this package's: ``load_model('DeepMIL', dims,
+      network='ABMIL' | 'MaxMIL' | 'MeanMIL' | 'DSMIL')`` (model/utils.py:67-91), i.e. ``SAHandler.func_load_model``, builds the
+      HIP baselines.
     * ``resident_bags=True``: ``dataset.utils.prepare_surv_dataset`` (and the name ``runner.sa_handler`` imported from it, if already
       loaded) wraps what it returns in ``vlsa_amd.ingest.ResidentBags`` -- every bag is read and uploaded ONCE, later epochs find it in
       HBM.  Stored as **fp32** here, bit for bit what dataset/PatchWSI.py:214 hands the handler (an "unmodified" reference run must
@@ -147,6 +179,10 @@ def patch_reference(resident_bags: bool = False, defer_training_calls: bool = Tr
     VLSA.defer_training_calls = defer_training_calls
     ref_mil.VLFAN, ref_mil.FeatMIL, ref_mil.DeepMIL = fast.VLFAN, fast.FeatMIL, fast.DeepMIL
     ref_mil.logit_pooling = ref_vlsa.logit_pooling = fast.logit_pooling
+    # the SA baselines' factory names (model/utils.py:6 imported them by name)
+    saved["sa_baselines"] = [(mod, attr, getattr(mod, attr, _ABSENT)) for mod, attr in
+                             ((ref_utils, "DeepMIL"), (ref_utils, "DSMIL"), (ref_mil, "DSMIL"))]
+    ref_utils.DeepMIL, ref_utils.DSMIL, ref_mil.DSMIL = fast.DeepMIL, fast.DSMIL, fast.DSMIL
     if resident_bags:
         import sys
         import dataset.utils as ref_ds
@@ -179,6 +215,12 @@ def unpatch_reference(saved) -> None:
     ref_utils.VLSA, ref_vlsa.VLSA = saved["VLSA_utils"], saved["VLSA_vlsa"]
     ref_mil.VLFAN, ref_mil.FeatMIL, ref_mil.DeepMIL = saved["VLFAN"], saved["FeatMIL"], saved["DeepMIL"]
     ref_mil.logit_pooling = ref_vlsa.logit_pooling = saved["logit_pooling"]
+    for mod, attr, original in saved.get("sa_baselines", ()):
+        if original is _ABSENT:
+            if hasattr(mod, attr):
+                delattr(mod, attr)
+        else:
+            setattr(mod, attr, original)
     VLSA.defer_training_calls = saved.get("defer_training_calls", False)
     if "prepare_surv_dataset" in saved:
         import sys

@@ -85,6 +85,11 @@ class ParanoidMismatch(RuntimeError):
 def build_mil_encoder(image_encoder_cfg: dict) -> nn.Module:
     """getattr(model.deepmil, cfg['name'])(**cfg)  (model/utils_vl.py:129-138)."""
     name = image_encoder_cfg["name"]
+    if name == "DSMIL":
+        # model/utils_vl.py builds it with num_cls = 2: its [1, 2] class logits cannot meet the [K, 512] text features of model/vlsa.py:185-192
+        raise ValueError("Got an invalid MIL encoder name: DSMIL. As a VLSA image encoder DSMIL returns [1, num_cls] class logits, not a "
+                         "[1, 512] visual feature that the text features could be compared with; it is served as the survival baseline "
+                         "load_model('DeepMIL', dims, network='DSMIL') instead.")
     cls = getattr(mil_encoders, name, None)
     if cls is None or name.startswith("_"):
         raise ValueError(f"Got an invalid MIL encoder name: {name}.")
