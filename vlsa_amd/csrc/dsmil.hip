@@ -31,10 +31,6 @@ constexpr int rows_per_group(int cp) { return cp <= 4 ? 4 : 2; }
 constexpr int kTileB = 32;        // rows per tile of the kernels that keep the tile in LDS (2 rows per group)
 constexpr float kInvSqrtH = 0.0625f;
 
-struct Bag {
-    const void* X;
-    long long N, ldx;
-};
 
 __device__ __forceinline__ void load8(const float* p, float* o) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
@@ -124,7 +120,7 @@ __device__ __forceinline__ void fill_queries(float* W, const float* src, int C, 
 
 // ---- pass 1: per part and class the largest instance score and its row -----------------------------------------------------------
 template <typename T, int CP>
-__global__ __launch_bounds__(kThreads) void k_dsmil_scores(const Bag* bags, int B, int C, const int* part_start, const float* Wc,
+__global__ __launch_bounds__(kThreads) void k_dsmil_scores(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* Wc,
                                                            float* pmax, int* pidx) {
     __shared__ float W[CP * kD];
     __shared__ float rv[16][CP];
@@ -179,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_scores(const Bag* bags, int 
 
 // ---- critical rows: one block per (bag, class) -----------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(kThreads) void k_dsmil_critical(const Bag* bags, int C, const int* part_start, const float* pmax,
+__global__ __launch_bounds__(kThreads) void k_dsmil_critical(const vlsa_bag_desc* bags, int C, const int* part_start, const float* pmax,
                                                              const int* pidx, const float* bc, const float* Wq, const float* bq,
                                                              int* crit, float* cmax, float* xcrit, float* qmax, float* u) {
     __shared__ float sv[kThreads];
@@ -310,7 +306,7 @@ __device__ __forceinline__ void write_weighted(float* scratch, const float (&acc
 
 // pass 2: per part (m, l, sum_n exp2(s - m) drop(x_n)) with the C rows of u as queries
 template <typename T, int CP, bool DROP>
-__global__ __launch_bounds__(kThreads) void k_dsmil_aggregate(const Bag* bags, int B, int C, const int* part_start, const float* u,
+__global__ __launch_bounds__(kThreads) void k_dsmil_aggregate(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
                                                               float drop_p, const long long* seed_word, float* pm, float* pl,
                                                               float* pacc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -459,7 +455,7 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_head(int C, const int* part_
 
 // ---- attention output: mean_k A[n,k], recomputed from the kept (m, l) --------------------------------------------------------------
 template <typename T, int CP>
-__global__ __launch_bounds__(kThreads) void k_dsmil_attn(const Bag* bags, int B, int C, const int* part_start, const float* u,
+__global__ __launch_bounds__(kThreads) void k_dsmil_attn(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
                                                          const float* m2, const float* l, float* attn, const long long* a_off) {
     __shared__ float U[CP * kD];
     int g, G;
@@ -520,7 +516,7 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_bwd_prep(int C, const float*
 
 // the streaming pass of the backward: per part sum_n ds[n,j] x_n with ds[n,j] = A[n,j] (drop(x_n) . dz_j - z_j . dz_j)
 template <typename T, int CP, bool DROP>
-__global__ __launch_bounds__(kThreads) void k_dsmil_bwd_stream(const Bag* bags, int B, int C, const int* part_start, const float* u,
+__global__ __launch_bounds__(kThreads) void k_dsmil_bwd_stream(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
                                                                const float* dz, const float* zdz, const float* m2, const float* l,
                                                                float drop_p, const long long* seed_word, float* pdu) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -761,7 +757,7 @@ extern "C" int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype
     if (rc != VLSA_OK) return rc;
     if (!Wc || !bc || !Wq || !bq || !Wv || !bv || !Wf || !bf || !ws || !state || !logits || (attn && !a_off)) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const Bag* bags = static_cast<const Bag*>(bag_desc);
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     const WsLayout w(n_parts, C);
     const StateLayout s(B, C);
     float* wsf = static_cast<float*>(ws);
@@ -831,7 +827,7 @@ extern "C" int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtyp
     if (rc != VLSA_OK) return rc;
     if (!Wq || !Wv || !Wf || !dlogits || !state || !ws || !dWc || !dbc || !dWq || !dbq || !dWv || !dbv || !dWf || !dbf) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const Bag* bags = static_cast<const Bag*>(bag_desc);
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     const WsLayout w(n_parts, C);
     const StateLayout s(B, C);
     float* wsf = static_cast<float*>(ws);

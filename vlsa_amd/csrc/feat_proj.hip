@@ -25,10 +25,6 @@
 
 namespace vlsa {
 
-typedef bf16x8 __attribute__((may_alias)) bf16x8_maf;
-typedef float __attribute__((may_alias)) float_maf;
-typedef f32x4 __attribute__((may_alias)) f32x4_maf;
-
 namespace fp {
 constexpr int kD = 512;                           // input and output width
 constexpr int kSteps = 16;                        // K steps of 32
@@ -123,7 +119,6 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)xbase)),
         0, __builtin_amdgcn_readfirstlane((int)(((long long)(nrows - 1) * ldx + kD) * XESZ)), 0x00020000);
     const int xvoff = (int)((long long)xr * ldx + xc * 8) * XESZ;
-    typedef int i32x4fp __attribute__((ext_vector_type(4)));
     struct XReg { bf16x8 h; f32x4 f[XF32 ? 2 : 1]; };
     auto load_x = [&](int ks) -> XReg {
         XReg r = {};
@@ -176,10 +171,10 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
                     h[e] = a;
                     l[e] = (__bf16)(v - (float)a);
                 }
-                *reinterpret_cast<bf16x8_maf*>(xb + x_dst) = h;
-                *reinterpret_cast<bf16x8_maf*>(xb + kXBuf + x_dst) = l;
+                *reinterpret_cast<bf16x8_ma*>(xb + x_dst) = h;
+                *reinterpret_cast<bf16x8_ma*>(xb + kXBuf + x_dst) = l;
             } else {
-                *reinterpret_cast<bf16x8_maf*>(xb + x_dst) = xcur.h;
+                *reinterpret_cast<bf16x8_ma*>(xb + x_dst) = xcur.h;
             }
         }
         __syncthreads();                     // X(s) published by every wave; everyone is done reading buffer (s + 1) & 1
@@ -190,8 +185,8 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
             bf16x8 A[2], AL[XF32 ? 2 : 1];
 #pragma unroll
             for (int r2 = 0; r2 < 2; ++r2) {
-                A[r2] = *reinterpret_cast<const bf16x8_maf*>(xb + (2 * q + r2) * 1024 + a_off);
-                if constexpr (XF32) AL[r2] = *reinterpret_cast<const bf16x8_maf*>(xb + kXBuf + (2 * q + r2) * 1024 + a_off);
+                A[r2] = *reinterpret_cast<const bf16x8_ma*>(xb + (2 * q + r2) * 1024 + a_off);
+                if constexpr (XF32) AL[r2] = *reinterpret_cast<const bf16x8_ma*>(xb + kXBuf + (2 * q + r2) * 1024 + a_off);
             }
             // hi terms of the 8 accumulators of this group, then the lo terms: MFMAs on one accumulator are 8 apart
 #pragma unroll
@@ -222,8 +217,8 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
     }
 
     // ---- epilogue: LayerNorm over the 512 columns of every row (8 waves x 64 columns), two passes
-    float_maf* scr = reinterpret_cast<float_maf*>(smem + kScrOff);     // [8 waves][ROWS]
-    float_maf* stat = reinterpret_cast<float_maf*>(smem + kStatOff);   // [ROWS]
+    float_ma* scr = reinterpret_cast<float_ma*>(smem + kScrOff);     // [8 waves][ROWS]
+    float_ma* stat = reinterpret_cast<float_ma*>(smem + kStatOff);   // [ROWS]
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -243,7 +238,7 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
     __syncthreads();
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const f32x4 mean = *reinterpret_cast<const f32x4_maf*>(&stat[16 * rt + 4 * g]);
+        const f32x4 mean = *reinterpret_cast<const f32x4_ma*>(&stat[16 * rt + 4 * g]);
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) acc[rt][ct] -= mean;
 #pragma unroll
@@ -274,7 +269,7 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
     }
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const f32x4 rstd = *reinterpret_cast<const f32x4_maf*>(&stat[16 * rt + 4 * g]);
+        const f32x4 rstd = *reinterpret_cast<const f32x4_ma*>(&stat[16 * rt + 4 * g]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 16 * rt + 4 * g + r;
@@ -295,16 +290,12 @@ __global__ __launch_bounds__(512) void k_feat_proj(const void* __restrict__ Xv, 
     fp_tile<XF32, RT>(smem, Xv, N, ldx, (long long)blockIdx.x * (16 * RT), prep, eps, Y, ldy, stats);
 }
 
-struct FpBag {                 // vlsa_bag_desc
-    const void* X;
-    long long N, ldx;
-};
 
 // The same tile for a TABLE of B <= 64 bags in one launch: workgroup t finds its bag from tile_start [B + 1] (tiles of 16 RT rows,
 // counted bag by bag) as the multi-bag kernels of mlp_backward.hip do, and writes to the packed output Y [sum N][512] / stats
 // [sum N][4], bag b at row row_off[b].  Everything that selects the rows is wave-uniform (scalar loads).
 template <bool XF32, int RT>
-__global__ __launch_bounds__(512) void k_feat_proj_bags(const FpBag* __restrict__ bags, int B, const int* __restrict__ tile_start,
+__global__ __launch_bounds__(512) void k_feat_proj_bags(const vlsa_bag_desc* __restrict__ bags, int B, const int* __restrict__ tile_start,
                                                          const long long* __restrict__ row_off, const unsigned char* __restrict__ prep,
                                                          float eps, float* __restrict__ Y, float* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(512) void k_feat_proj_bags(const FpBag* __restrict_
     const int ts = lane < B ? tile_start[lane] : 0x7fffffff;
     const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1);
     if (b < 0) return;
-    const FpBag bag = bags[b];
+    const vlsa_bag_desc bag = bags[b];
     const long long row0 = (long long)(t - tile_start[b]) * (16 * RT);
     if (row0 >= bag.N) return;              // (a table that does not match the grid: nothing is read or written)
     const long long off = row_off[b];
@@ -400,7 +391,7 @@ extern "C" int vlsa_feat_project_batch(const void* bag_desc, int B, int x_dtype,
     if (tile_rows != 32 && tile_rows != 64 && !(tile_rows == 128 && !f32)) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    const FpBag* bags = static_cast<const FpBag*>(bag_desc);
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     const long long* ro = reinterpret_cast<const long long*>(row_off);
 #define VLSA_FPB(X32, RT_)                                                                                                        \
     hipLaunchKernelGGL((k_feat_proj_bags<X32, RT_>), dim3((unsigned int)n_tiles), dim3(512), fp::kLds, st, bags, B, tile_start, ro, pp, \

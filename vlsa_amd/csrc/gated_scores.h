@@ -58,12 +58,8 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
-struct GsBag {
-    const void* X;
-    long long N, ldx;
-};
 struct GsBatch {
-    const GsBag* bags;
+    const vlsa_bag_desc* bags;
     const int* tile_start;      // [B + 1], tile_start[0] = 0
     const long long* a_off;     // [B] offset (floats) of bag b's scores in a_out
     int B;                      // <= 64

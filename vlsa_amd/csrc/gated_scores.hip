@@ -54,11 +54,6 @@
 
 namespace vlsa {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr_g;
-typedef bf16x8 __attribute__((may_alias)) bf16x8_mag;
-typedef float __attribute__((may_alias)) float_mag;
-typedef int i32x4g __attribute__((ext_vector_type(4)));
-
 namespace gs {
 constexpr int kRows = 256;                        // patch rows per workgroup tile
 constexpr int kXBuf = kRows * 64;                 // one K step of the tile: 256 rows x 32 bf16 = 16 KiB
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
         const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
         const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= tile)) - 1;
         if (GATED && bt.seed_word != nullptr) drop_seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
-        const GsBag bag = bt.bags[b];
+        const vlsa_bag_desc bag = bt.bags[b];
         Xv = bag.X;
         N = bag.N;
         ldx = bag.ldx;
@@ -293,12 +288,12 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
                     h[e] = a;
                     l[e] = (__bf16)(v - (float)a);
                 }
-                *reinterpret_cast<bf16x8_mag*>(xb + (j ? x_dst1 : x_dst0)) = h;
-                *reinterpret_cast<bf16x8_mag*>(xb + XIS + (j ? x_dst1 : x_dst0)) = l;
+                *reinterpret_cast<bf16x8_ma*>(xb + (j ? x_dst1 : x_dst0)) = h;
+                *reinterpret_cast<bf16x8_ma*>(xb + XIS + (j ? x_dst1 : x_dst0)) = l;
             }
         } else if (!(VLSA_GS_ABL & (4 | 128)) || s < 2) {
 #pragma unroll
-            for (int j = 0; j < XCH; ++j) *reinterpret_cast<bf16x8_mag*>(xb + (xr + j * XRS) * 64 + (((xc + j * XCS) ^ fx) << 4)) = xcur.c[j];
+            for (int j = 0; j < XCH; ++j) *reinterpret_cast<bf16x8_ma*>(xb + (xr + j * XRS) * 64 + (((xc + j * XCS) ^ fx) << 4)) = xcur.c[j];
         } else if (VLSA_GS_ABL & 128) {
 #pragma unroll
             for (int j = 0; j < XCH; ++j) asm volatile("" ::"v"(xcur.c[j]));
@@ -314,9 +309,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
 #pragma unroll
             for (int r4 = 0; r4 < AQ; ++r4) {
                 if ((VLSA_GS_ABL & 1) && (s > 0 || q > 0)) { A[r4] = abl_a[r4]; continue; }
-                A[r4] = *reinterpret_cast<const bf16x8_mag*>(xb + (AQ * q + r4) * 1024 + a_off);
+                A[r4] = *reinterpret_cast<const bf16x8_ma*>(xb + (AQ * q + r4) * 1024 + a_off);
                 if (VLSA_GS_ABL & 1) abl_a[r4] = A[r4];
-                if constexpr (XF32) AL[r4] = *reinterpret_cast<const bf16x8_mag*>(xb + XIS + (AQ * q + r4) * 1024 + a_off);
+                if constexpr (XF32) AL[r4] = *reinterpret_cast<const bf16x8_ma*>(xb + XIS + (AQ * q + r4) * 1024 + a_off);
             }
             if (AQ * q + AQ <= nrt) {
                 // hi terms of the 4 NB accumulators of this group, then the lo terms: MFMAs on one accumulator are 4 NB apart
@@ -390,7 +385,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
 
     // ---- epilogue: activations, gate, w2, sum over this wave's 16 hidden units, then over the 8 waves, then (atomically) over
     // the two workgroups that share the row tile
-    float_mag* scr = reinterpret_cast<float_mag*>(smem + ((XF32 && !XSMALL) ? kScrOff32 : kScrOff));
+    float_ma* scr = reinterpret_cast<float_ma*>(smem + ((XF32 && !XSMALL) ? kScrOff32 : kScrOff));
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
         if (rt < nrt)
@@ -665,7 +660,7 @@ static int gated_scores_batch_impl(const void* bag_desc, int B, int x_dtype, int
                                    int64_t a_floats, float drop_p, const int64_t* seed_word, void* stream) {
     if (!bag_desc || !prep || !a || !tile_start || !a_off || B < 1 || B > 64 || n_tiles < 1 || a_floats < 1) return VLSA_EINVAL;
     if (D != gs::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
-    GsBatch bt{static_cast<const GsBag*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u, nullptr};
+    GsBatch bt{static_cast<const vlsa_bag_desc*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u, nullptr};
     if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_train; the seed comes from the device word
         if (!(drop_p < 1.f) || !seed_word) return VLSA_EINVAL;
         bt.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
@@ -754,7 +749,7 @@ extern "C" int vlsa_gated_scores_pool_batch(const void* bag_desc, int B, int x_d
                                             float* ws, float* pooled, void* stream) {
     if (!bag_desc || !prep || !a || !tile_start || !a_off || !ws || !pooled || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
     if (D != gs::kD || x_dtype != VLSA_DT_BF16) return VLSA_EUNSUPPORTED;
-    const GsBatch bt{static_cast<const GsBag*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u};
+    const GsBatch bt{static_cast<const vlsa_bag_desc*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u};
     return gs_tile_launch(nullptr, 0ll, 0ll, static_cast<const unsigned char*>(prep), gated, a, n_tiles, rows_per_tile, bt, ws, pooled,
                           (hipStream_t)stream);
 }

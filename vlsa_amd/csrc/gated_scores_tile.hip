@@ -49,11 +49,6 @@ extern "C" int vlsa_debug_gt_stamps(long long* out) {
 
 namespace vlsa {
 
-typedef bf16x8 __attribute__((may_alias)) bf16x8_mat;
-typedef float __attribute__((may_alias)) float_mat;
-typedef int i32x4t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_void_ptr_t;
-
 namespace gt {
 constexpr int kCols = 256;              // columns (hidden unit, branch) per workgroup
 constexpr int kB = 2 * kCols * 64;      // weight block of a K step: hi image + lo image, 32 KiB
@@ -159,16 +154,16 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
     const int first = (GATED && !SEQ) ? ((bid >> 4) << 3) + (bid & 7) : bid;
     const int stride = (GATED && !SEQ) ? (int)(gridDim.x >> 1) : (int)gridDim.x;     // walkers
 
-    i32x4t wrs;             // both column halves' weight blocks: half hv at hv * 16 * kB
+    i32x4 wrs;             // both column halves' weight blocks: half hv at hv * 16 * kB
     const unsigned long long waddr = reinterpret_cast<unsigned long long>(prep + L.wtile);
     wrs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned int)waddr);
     wrs[1] = __builtin_amdgcn_readfirstlane((int)((waddr >> 32) & 0xffffu));
     wrs[2] = (GATED ? 2 : 1) * gs::kSteps * kB;
     wrs[3] = 0x00020000;
-    const unsigned int lds0 = (unsigned int)(uintptr_t)(lds_void_ptr_t)smem;
+    const unsigned int lds0 = (unsigned int)(uintptr_t)(lds_void_ptr)smem;
 
     // a tile's X source, all of it wave-uniform (SGPRs): the descriptor over its rows, the row pitch, where its scores go
-    struct Src { i32x4t rs; int ldb; float* a; long long row0; int nrows, n0, n1; const unsigned char* x0; unsigned int seed; };   // n0, n1: 16-row tiles of row half 0 / 1
+    struct Src { i32x4 rs; int ldb; float* a; long long row0; int nrows, n0, n1; const unsigned char* x0; unsigned int seed; };   // n0, n1: 16-row tiles of row half 0 / 1
     const int xr = lane >> 2;
     const int xchunk = ((lane & 3) ^ ((0 - (xr >> 2)) & 3)) << 4;
     // Who stages what: wave w LDS row blocks w and w + 8 and pieces w, w + 8, w + 16, w + 24 of the step's weight block.  (The SIMD's
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
             const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
             const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
             if (GATED && bt.seed_word != nullptr) seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
-            const GsBag bag = bt.bags[b];
+            const vlsa_bag_desc bag = bt.bags[b];
             Xv = bag.X;
             N = bag.N;
             ldx = bag.ldx;
@@ -228,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
         if (j < NJA) {
             const int b = wi + JW * j, hb = b & 7;                   // (uniform)
             const int tb = b < 8 ? b : sc.n0 + hb;
-            i32x4t d = sc.rs;
+            i32x4 d = sc.rs;
             d[2] = __builtin_amdgcn_readfirstlane(hb < (b < 8 ? sc.n0 : sc.n1) ? sc.rs[2] : 0);
             VLSA_GT_DMA(sa + b * 1024, (16 * tb + xr) * sc.ldb + xchunk, d, ks * 64);
         } else {
@@ -253,8 +248,8 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
     // the workgroup's constants live in LDS (registers are what this kernel is short of): per column half [256] bias of the tile's
     // columns and [256] w2 of the columns' hidden units; c; behind them the tile's scores [256 LDS rows] (SEQ / POOL)
     constexpr int NH = GATED ? 2 : 4;
-    float_mat* cst = reinterpret_cast<float_mat*>(smem + kRing + 4096);
-    float_mat* tsc = cst + 1040;
+    float_ma* cst = reinterpret_cast<float_ma*>(smem + kRing + 4096);
+    float_ma* tsc = cst + 1040;
     {
         const int hh = tid >> 8, ct256 = tid & 255;            // 512 threads: column half, column
         const int cn = ct256 >> 6, ct = (ct256 >> 4) & 3, ci = ct256 & 15;
@@ -269,8 +264,8 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
 
     const int frag = i16 * 64 + ((g ^ ((0 - (i16 >> 2)) & 3)) << 4);
     const int a_frag = 128 * wm * 64 + frag, b_frag = kA + (64 * wn) * 64 + frag;
-    auto rd = [&](const unsigned char* p) { return *reinterpret_cast<const bf16x8_mat*>(p); };
-    float_mat* scr = reinterpret_cast<float_mat*>(smem + kRing);    // [4 column quarters][256 LDS rows]
+    auto rd = [&](const unsigned char* p) { return *reinterpret_cast<const bf16x8_ma*>(p); };
+    float_ma* scr = reinterpret_cast<float_ma*>(smem + kRing);    // [4 column quarters][256 LDS rows]
 
     // one iteration = one PASS: 16 K steps of one column half over one row tile (SEQ: two passes per tile)
 #pragma unroll 1

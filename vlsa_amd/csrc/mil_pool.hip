@@ -82,15 +82,11 @@ __global__ __launch_bounds__(256) void k_scored_pool_partial(const XT* __restric
 // 16-byte loads; 4 rows per wave are in flight before the (sequential) online-softmax update.  Same outputs as above.
 // Several bags per launch: grid (G, B); bags != null: workgroup (g, bag) pools rows_of_block(N_bag, g, G) of bag blockIdx.y with
 // the scores at scores + a_off[bag] and writes partial bag * G + g.
-struct PoolBag {
-    const void* X;
-    long long N, ldx;
-};
 template <typename XT, int NC>
 __global__ __launch_bounds__(256) void k_scored_pool_partial_vec(const XT* __restrict__ X, int64_t N, int64_t ldx, int D,
                                                                   const float* __restrict__ scores, float* __restrict__ pm,
                                                                   float* __restrict__ pl, float* __restrict__ pacc, int G,
-                                                                  const PoolBag* __restrict__ bags,
+                                                                  const vlsa_bag_desc* __restrict__ bags,
                                                                   const long long* __restrict__ a_off) {
     constexpr int VEC = 16 / (int)sizeof(XT);
     constexpr int U = 4;
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(256) void k_scored_pool_partial_vec(const XT* __res
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int b = blockIdx.x;
     if (bags != nullptr) {
-        const PoolBag bag = bags[blockIdx.y];
+        const vlsa_bag_desc bag = bags[blockIdx.y];
         X = static_cast<const XT*>(bag.X);
         N = bag.N;
         ldx = bag.ldx;
@@ -532,21 +528,12 @@ __global__ __launch_bounds__(256) void k_topk_mean(const float* __restrict__ S, 
 }
 // B bags per launch: workgroup (class, bag) pools row `class` of bag's score matrix ([C, ld] fp32, e.g. the per-class cosines
 // the batched streaming kernel stored); k is clamped to the bag's N (k >= N: plain mean).  out [B, C] *= exp(*logit_scale).
-struct TopkBagDesc {
-    const void* X;
-    int64_t N;
-    int64_t ldx;
-};
-struct TopkRowsDesc {
-    float* ptr;
-    int64_t ld;
-};
-__global__ __launch_bounds__(256) void k_topk_mean_batch(const TopkBagDesc* __restrict__ bags, const TopkRowsDesc* __restrict__ sdesc,
+__global__ __launch_bounds__(256) void k_topk_mean_batch(const vlsa_bag_desc* __restrict__ bags, const vlsa_rows_desc* __restrict__ sdesc,
                                                           int C, int k, const float* __restrict__ logit_scale,
                                                           float* __restrict__ out) {
     const int cls = blockIdx.x, bag = blockIdx.y;
     const int64_t N = bags[bag].N;
-    const TopkRowsDesc sd = sdesc[bag];
+    const vlsa_rows_desc sd = sdesc[bag];
     if (N <= 0 || sd.ptr == nullptr) {
         if (threadIdx.x == 0) out[(size_t)bag * C + cls] = 0.f;
         return;
@@ -714,7 +701,7 @@ static int launch_scored(const XT* X, int64_t N, int64_t ldx, int D, const float
     {                                                                                                                   \
         const size_t lds = (8 + (size_t)4 * NCV * 64 * VEC) * sizeof(float);                                            \
         hipLaunchKernelGGL((k_scored_pool_partial_vec<XT, NCV>), dim3(G), dim3(256), lds, s, X, N, ldx, D, scores, pm, pl, pacc, G, \
-                           static_cast<const PoolBag*>(nullptr), static_cast<const long long*>(nullptr));                    \
+                           static_cast<const vlsa_bag_desc*>(nullptr), static_cast<const long long*>(nullptr));                    \
     }
         if (NC == 1) VLSA_SPV(1) else if (NC == 2) VLSA_SPV(2) else if (NC == 3) VLSA_SPV(3) else VLSA_SPV(4)
 #undef VLSA_SPV
@@ -742,7 +729,7 @@ extern "C" int vlsa_scored_pool_partial_batch(const void* bag_desc, int B, int x
     if (!bag_desc || !pm || !pl || !pacc || B < 1 || G < 1 || (scores && !a_off)) return VLSA_EINVAL;
     if (D != 512 || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    const PoolBag* bags = static_cast<const PoolBag*>(bag_desc);
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     const long long* off = reinterpret_cast<const long long*>(a_off);
     if (x_dtype == VLSA_DT_F32) {
         const size_t lds = (8 + (size_t)4 * 2 * 64 * 4) * sizeof(float);
@@ -904,8 +891,8 @@ extern "C" int vlsa_topk_mean_batch(const void* bag_desc, const void* scores_des
     if (!bag_desc || !scores_desc || !out || B < 1 || C < 1) return VLSA_EINVAL;
     if (k > kTopKMax) return VLSA_EUNSUPPORTED;
     const int kk = k <= 0 ? 0x7fffffff : k;      // mean over all patches
-    hipLaunchKernelGGL(k_topk_mean_batch, dim3(C, B), dim3(256), 0, (hipStream_t)stream, static_cast<const TopkBagDesc*>(bag_desc),
-                       static_cast<const TopkRowsDesc*>(scores_desc), C, kk, logit_scale, out);
+    hipLaunchKernelGGL(k_topk_mean_batch, dim3(C, B), dim3(256), 0, (hipStream_t)stream, static_cast<const vlsa_bag_desc*>(bag_desc),
+                       static_cast<const vlsa_rows_desc*>(scores_desc), C, kk, logit_scale, out);
     return st();
 }
 

@@ -31,13 +31,6 @@
 
 namespace vlsa {
 
-typedef bf16x8 __attribute__((may_alias)) bf16x8_mb;
-typedef bf16x4 __attribute__((may_alias)) bf16x4_mb;
-typedef f32x4 __attribute__((may_alias)) f32x4_mb;
-typedef float __attribute__((may_alias)) float_mb;
-typedef unsigned int u32x4_mb_t __attribute__((ext_vector_type(4)));
-typedef u32x4_mb_t __attribute__((may_alias)) u32x4_mb;
-
 namespace mb {
 constexpr int kD = 512;
 constexpr int kTileBytes = 65536;            // bf16: 64 rows x 1 KiB; fp32: hi + lo bf16 images of 32 rows
@@ -48,14 +41,10 @@ constexpr int kDyPitch = 132;
 enum { kTanh = 0, kGated = 1, kLN = 2 };
 }  // namespace mb
 
-struct MbBag {
-    const void* X;
-    long long N, ldx;
-};
 
 struct MbArgs {
-    const MbBag* bags;          // [B] rows of the layer input
-    const MbBag* dy;            // projecter: [B] upstream gradient rows (fp32 [N, 512]); else null
+    const vlsa_bag_desc* bags;          // [B] rows of the layer input
+    const vlsa_bag_desc* dy;            // projecter: [B] upstream gradient rows (fp32 [N, 512]); else null
     const int* tile_start;      // [B + 1] first row tile of every bag (tiles of mb rows: 64 bf16 / 32 fp32)
     const long long* row_off;   // [B] offset of bag b's rows in `rowvec`
     const float* rowvec;        // scores: da [sum N]; projecter: stats [sum N][4] = (mean, rstd, c1, c2)
@@ -132,7 +121,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
     auto find = [&](int t) -> Tile {
         const int ts = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
         const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
-        const MbBag bag = a.bags[b];
+        const vlsa_bag_desc bag = a.bags[b];
         const long long row0 = (long long)(t - a.tile_start[b]) * ROWS;
         Tile r;
         r.b = b;
@@ -151,29 +140,29 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
         r.dy = nullptr;
         r.lddy = 0;
         if constexpr (MODE == kLN) {
-            const MbBag d = a.dy[b];
+            const vlsa_bag_desc d = a.dy[b];
             r.dy = static_cast<const float*>(d.X) + row0 * d.ldx;
             r.lddy = d.ldx;
         }
         return r;
     };
-    u32x4_mb_t st[8];
-    u32x4_mb_t sd[MODE == kLN ? (XF32 ? 2 : 4) : 1];
+    u32x4 st[8];
+    u32x4 sd[MODE == kLN ? (XF32 ? 2 : 4) : 1];
     auto stage_load = [&](const Tile& T) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int p = tid + 512 * k;
             const int row = XF32 ? (p >> 7) : (p >> 6), ch = XF32 ? (p & 127) : (p & 63);
-            st[k] = u32x4_mb_t{0u, 0u, 0u, 0u};
-            if (row < T.nrows) st[k] = *reinterpret_cast<const u32x4_mb_t*>(T.x + ((size_t)row * T.ldx * (XF32 ? 4 : 2)) + ch * 16);
+            st[k] = u32x4{0u, 0u, 0u, 0u};
+            if (row < T.nrows) st[k] = *reinterpret_cast<const u32x4*>(T.x + ((size_t)row * T.ldx * (XF32 ? 4 : 2)) + ch * 16);
         }
         if constexpr (MODE == kLN) {          // this slice's 128 columns of dy: [ROWS][128] fp32
 #pragma unroll
             for (int k = 0; k < (XF32 ? 2 : 4); ++k) {
                 const int p = tid + 512 * k;
                 const int row = p >> 5, ch = p & 31;
-                sd[k] = u32x4_mb_t{0u, 0u, 0u, 0u};
-                if (row < T.nrows) sd[k] = *reinterpret_cast<const u32x4_mb_t*>(T.dy + (size_t)row * T.lddy + 128 * sl + 4 * ch);
+                sd[k] = u32x4{0u, 0u, 0u, 0u};
+                if (row < T.nrows) sd[k] = *reinterpret_cast<const u32x4*>(T.dy + (size_t)row * T.lddy + 128 * sl + 4 * ch);
             }
         }
     };
@@ -192,11 +181,11 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                     lo[e] = (__bf16)(f - (float)hi[e]);
                 }
                 const int off = (c4 >> 5) * QB + mb_swz(row, (c4 & 31) * 8);
-                *reinterpret_cast<bf16x4_mb*>(smem + off) = hi;
-                *reinterpret_cast<bf16x4_mb*>(smem + IMG + off) = lo;
+                *reinterpret_cast<bf16x4_ma*>(smem + off) = hi;
+                *reinterpret_cast<bf16x4_ma*>(smem + IMG + off) = lo;
             } else {
                 const int row = p >> 6, ch = p & 63;
-                *reinterpret_cast<u32x4_mb*>(smem + (ch >> 4) * QB + mb_swz(row, (ch & 15) * 16)) = st[k];
+                *reinterpret_cast<u32x4_ma*>(smem + (ch >> 4) * QB + mb_swz(row, (ch & 15) * 16)) = st[k];
             }
         }
         if constexpr (MODE == kLN) {
@@ -204,7 +193,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
             for (int k = 0; k < (XF32 ? 2 : 4); ++k) {
                 const int p = tid + 512 * k;
                 const int row = p >> 5, ch = p & 31;
-                *reinterpret_cast<u32x4_mb*>(smem + kExchOff + (row * kDyPitch + 4 * ch) * 4) = sd[k];
+                *reinterpret_cast<u32x4_ma*>(smem + kExchOff + (row * kDyPitch + 4 * ch) * 4) = sd[k];
             }
         }
     };
@@ -228,7 +217,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                     dpv[e] = dpb[e];
                     cst = fmaf(plb[e], dpv[e], cst);
                 }
-                float_mb* pd = reinterpret_cast<float_mb*>(smem + kExchOff + 32768);
+                float_ma* pd = reinterpret_cast<float_ma*>(smem + kExchOff + 32768);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     float d = -cst;
@@ -259,8 +248,8 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                     bf16x8 A[RT], AL[XF32 ? RT : 1];
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
-                        A[rt] = *reinterpret_cast<const bf16x8_mb*>(smem + qoff + mb_swz(16 * rt + i16, boff));
-                        if constexpr (XF32) AL[rt] = *reinterpret_cast<const bf16x8_mb*>(smem + IMG + qoff + mb_swz(16 * rt + i16, boff));
+                        A[rt] = *reinterpret_cast<const bf16x8_ma*>(smem + qoff + mb_swz(16 * rt + i16, boff));
+                        if constexpr (XF32) AL[rt] = *reinterpret_cast<const bf16x8_ma*>(smem + IMG + qoff + mb_swz(16 * rt + i16, boff));
                     }
 #pragma unroll
                     for (int term = 0; term < 2; ++term)
@@ -288,7 +277,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 if constexpr (POOL) {
-                    const float_mb* pd = reinterpret_cast<const float_mb*>(smem + kExchOff + 32768);
+                    const float_ma* pd = reinterpret_cast<const float_ma*>(smem + kExchOff + 32768);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = 16 * rt + 4 * g + r;
@@ -334,7 +323,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                     }
                 if constexpr (MODE == kGated) {
 #pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<f32x4_mb*>(ex + br * 4096 + (rt * 64 + lane) * 16) = acch[rt];
+                    for (int rt = 0; rt < RT; ++rt) *reinterpret_cast<f32x4_ma*>(ex + br * 4096 + (rt * 64 + lane) * 16) = acch[rt];
                     __syncthreads();
                 }
             }
@@ -347,12 +336,12 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
                 for (int h = 0; h < 2; ++h) {
                     const int rt = 2 * q32 + h;
                     f32x4 other = f32x4{1.f, 1.f, 1.f, 1.f};
-                    if constexpr (MODE == kGated) other = *reinterpret_cast<const f32x4_mb*>(ex + (br ^ 1) * 4096 + (rt * 64 + lane) * 16);
+                    if constexpr (MODE == kGated) other = *reinterpret_cast<const f32x4_ma*>(ex + (br ^ 1) * 4096 + (rt * 64 + lane) * 16);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float d;
                         if constexpr (MODE == kLN) {
-                            const float_mb* dys = reinterpret_cast<const float_mb*>(smem + kExchOff);
+                            const float_ma* dys = reinterpret_cast<const float_ma*>(smem + kExchOff);
                             const int row = 16 * rt + 4 * g + r;
                             const float dyv = dys[row * kDyPitch + 16 * w + i16];     // 0 for rows past the bag's end
                             f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};                       // (mean, rstd, c1, c2) of the row
@@ -484,7 +473,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_rowstats(const float* __restrict
 
 // The same over the packed rows of B <= 64 bags (y [total][512], stats [total][4], bag b at row row_off[b]) whose gradient rows
 // arrive as one matrix per bag: dyb [B] = {pointer, N, row stride}.
-__global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const MbBag* __restrict__ dyb, int B, const long long* __restrict__ row_off,
+__global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const vlsa_bag_desc* __restrict__ dyb, int B, const long long* __restrict__ row_off,
                                                                const float* __restrict__ y, long long total,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                float* __restrict__ stats) {
@@ -494,7 +483,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const MbBag* __res
     const long long ro = lane < B ? row_off[lane] : 0x7fffffffffffffffll;
     const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ro <= row)) - 1);
     if (b < 0) return;
-    const MbBag g = dyb[b];
+    const vlsa_bag_desc g = dyb[b];
     const long long r = row - row_off[b];
     if (r >= g.N) return;                     // (a table that does not cover the row: nothing is read)
     ln_bwd_row(static_cast<const float*>(g.X) + r * g.ldx, y + row * 512, gamma, beta, stats + row * 4, lane);
@@ -555,7 +544,7 @@ extern "C" int vlsa_attn_scores_backward(const void* bag_desc, int B, int x_dtyp
     const GatedPrepOffsets L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
-    a.bags = static_cast<const MbBag*>(bag_desc);
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     a.tile_start = tile_start;
     a.row_off = reinterpret_cast<const long long*>(a_off);
     a.rowvec = da;
@@ -609,7 +598,7 @@ extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_
     const GatedPrepOffsets L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
-    a.bags = static_cast<const MbBag*>(bag_desc);
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     a.tile_start = tile_start;
     a.row_off = reinterpret_cast<const long long*>(a_off);
     a.rowvec = a_raw;
@@ -672,7 +661,7 @@ extern "C" int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, cons
     const FeatProjOffsets L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     hipLaunchKernelGGL(k_ln_bwd_rowstats_bags, dim3((unsigned int)((total_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const MbBag*>(dy_desc), B, reinterpret_cast<const long long*>(row_off), y, (long long)total_rows,
+                       static_cast<const vlsa_bag_desc*>(dy_desc), B, reinterpret_cast<const long long*>(row_off), y, (long long)total_rows,
                        reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta), stats);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
@@ -689,8 +678,8 @@ extern "C" int vlsa_feat_project_backward(const void* bag_desc, const void* dy_d
     const FeatProjOffsets L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
-    a.bags = static_cast<const MbBag*>(bag_desc);
-    a.dy = static_cast<const MbBag*>(dy_desc);
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    a.dy = static_cast<const vlsa_bag_desc*>(dy_desc);
     a.tile_start = tile_start;
     a.row_off = reinterpret_cast<const long long*>(row_off);
     a.rowvec = stats;
@@ -747,8 +736,8 @@ __global__ __launch_bounds__(64) void k_prepare_attn_dx_weights(const float* __r
 }
 
 struct AdxArgs {
-    const MbBag* bags;          // [B] rows (bf16 or fp32)
-    const MbBag* dxs;           // [B] fp32 gradient rows to write
+    const vlsa_bag_desc* bags;          // [B] rows (bf16 or fp32)
+    const vlsa_bag_desc* dxs;           // [B] fp32 gradient rows to write
     const int* tile_start;      // [B + 1] tiles of 64 (bf16) / 32 (fp32) rows
     const long long* row_off;   // [B] offset of bag b's rows in da / aw
     const float* da;            // dL/da
@@ -779,7 +768,7 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
     // tile lookup
     const int tsv = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
     const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(tsv <= t)) - 1;
-    const MbBag bag = a.bags[b], ob = a.dxs[b];
+    const vlsa_bag_desc bag = a.bags[b], ob = a.dxs[b];
     const long long row0 = (long long)(t - a.tile_start[b]) * ROWS;
     const int nrows = (int)((bag.N - row0) < ROWS ? (bag.N - row0) : ROWS);
     const unsigned char* xsrc = static_cast<const unsigned char*>(bag.X) + row0 * bag.ldx * (XF32 ? 4 : 2);
@@ -791,8 +780,8 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
     for (int k = 0; k < 8; ++k) {
         const int p = tid + 512 * k;
         const int row = XF32 ? (p >> 7) : (p >> 6), ch = XF32 ? (p & 127) : (p & 63);
-        u32x4_mb_t v = u32x4_mb_t{0u, 0u, 0u, 0u};
-        if (row < nrows) v = *reinterpret_cast<const u32x4_mb_t*>(xsrc + ((size_t)row * bag.ldx * (XF32 ? 4 : 2)) + ch * 16);
+        u32x4 v = u32x4{0u, 0u, 0u, 0u};
+        if (row < nrows) v = *reinterpret_cast<const u32x4*>(xsrc + ((size_t)row * bag.ldx * (XF32 ? 4 : 2)) + ch * 16);
         if constexpr (XF32) {
             bf16x4 hi, lo;
 #pragma unroll
@@ -803,10 +792,10 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
                 lo[e] = (__bf16)(f - (float)hi[e]);
             }
             const int off = (ch >> 5) * QB + mb_swz(row, (ch & 31) * 8);
-            *reinterpret_cast<bf16x4_mb*>(smem + off) = hi;
-            *reinterpret_cast<bf16x4_mb*>(smem + 65536 + off) = lo;
+            *reinterpret_cast<bf16x4_ma*>(smem + off) = hi;
+            *reinterpret_cast<bf16x4_ma*>(smem + 65536 + off) = lo;
         } else {
-            *reinterpret_cast<u32x4_mb*>(smem + (ch >> 4) * QB + mb_swz(row, (ch & 15) * 16)) = v;
+            *reinterpret_cast<u32x4_ma*>(smem + (ch >> 4) * QB + mb_swz(row, (ch & 15) * 16)) = v;
         }
     }
     __syncthreads();
@@ -837,9 +826,9 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
             const int qoff = (ks >> 2) * QB, boff = (ks & 3) * 64 + g * 16;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                const bf16x8 A = *reinterpret_cast<const bf16x8_mb*>(smem + qoff + mb_swz(16 * rt + i16, boff));
+                const bf16x8 A = *reinterpret_cast<const bf16x8_ma*>(smem + qoff + mb_swz(16 * rt + i16, boff));
                 bf16x8 AL = A;
-                if constexpr (XF32) AL = *reinterpret_cast<const bf16x8_mb*>(smem + 65536 + qoff + mb_swz(16 * rt + i16, boff));
+                if constexpr (XF32) AL = *reinterpret_cast<const bf16x8_ma*>(smem + 65536 + qoff + mb_swz(16 * rt + i16, boff));
 #pragma unroll
                 for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
@@ -921,8 +910,8 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
             const int qoff = (ks >> 2) * QB, boff = (ks & 3) * 64 + g * 16;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                const bf16x8 Ah = *reinterpret_cast<const bf16x8_mb*>(smem + qoff + mb_swz(16 * rt + i16, boff));
-                const bf16x8 Al = *reinterpret_cast<const bf16x8_mb*>(smem + 65536 + qoff + mb_swz(16 * rt + i16, boff));
+                const bf16x8 Ah = *reinterpret_cast<const bf16x8_ma*>(smem + qoff + mb_swz(16 * rt + i16, boff));
+                const bf16x8 Al = *reinterpret_cast<const bf16x8_ma*>(smem + 65536 + qoff + mb_swz(16 * rt + i16, boff));
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
                     acco[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bc[ct][0], acco[rt][ct], 0, 0, 0);
@@ -985,8 +974,8 @@ static int attn_scores_backward_dx_impl(const void* bag_desc, const void* dx_des
     const GatedPrepOffsets L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     AdxArgs a{};
-    a.bags = static_cast<const MbBag*>(bag_desc);
-    a.dxs = static_cast<const MbBag*>(dx_desc);
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    a.dxs = static_cast<const vlsa_bag_desc*>(dx_desc);
     a.tile_start = tile_start;
     a.row_off = reinterpret_cast<const long long*>(a_off);
     a.da = da;

@@ -12,25 +12,13 @@
 // The two partial tiles a wave must share per 32-row tile (scores and dout . x) are exchanged in a compact
 // [2 h][4 g][12 p] layout so that a workgroup stays inside 80 KiB of LDS, hence P <= 12 here (the reference's datasets use
 // 7..12 prototypes); larger P goes through the per-bag kernel.
-#include "vlsa_common.h"
 #ifndef VLSA_DMA_NT
 #define VLSA_DMA_NT "nt"      // streaming rows: non-temporal (measurement builds may pass -DVLSA_DMA_NT=\"\")
 #endif
+#define VLSA_STREAM_NT VLSA_DMA_NT
+#include "vlfan_stream.h"
 
 namespace vlsa {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef bf16x8 __attribute__((may_alias)) bf16x8_ma;
-typedef f32x4 __attribute__((may_alias)) f32x4_ma;
-typedef float __attribute__((may_alias)) float_ma;
-typedef int __attribute__((may_alias)) int_ma;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-struct BagDesc {
-    const void* X;
-    int64_t N;
-    int64_t ldx;
-};
 
 namespace bb {
 constexpr int kTile = 32;
@@ -42,18 +30,10 @@ constexpr int kTileBytes = 2 * 4 * kMaxP * 16;    // one compact [2 h][4 g][12 p
 constexpr int kExchWave = 2 * kTileBytes + 128;   // S tile + dA tile + 32 row sums of squares = 3200 B
 constexpr int kExchGroup = 4 * kExchWave;
 constexpr int kTabOff = kRingBytes + kExchGroup;
+constexpr int kTabInts = 8;                       // the stream-descriptor ints
 constexpr int kMaxBags = 64;
-constexpr int kLdsBytes = kTabOff + kMaxBags * 32;  // 80,384 B: two workgroups per CU
+constexpr int kLdsBytes = kTabOff + kMaxBags * kTabInts * 4;  // 80,384 B: two workgroups per CU
 }  // namespace bb
-
-__device__ __forceinline__ int wswz(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
-
-#define VLSA_WBAR()                                          \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-    } while (0)
 
 // dsplit[bag][t][p][:] = 3-term bf16 split of dout[bag][p][:]; delta[bag][p] = dout . out     grid (16, B)
 __global__ __launch_bounds__(256) void k_prepare_backward_batch(const float* __restrict__ dout, const float* __restrict__ out,
@@ -82,7 +62,7 @@ __global__ __launch_bounds__(256) void k_prepare_backward_batch(const float* __r
 // S = number of workgroup groups: bag t is streamed by the Gb = G / S workgroups of group t % S only, so S bags are in
 // flight at once, every workgroup sees S times more rows per bag (fewer bag epilogues, better tile quantisation) and a
 // bag leaves Gb instead of G partials behind.
-__global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDesc* __restrict__ bags, int B,
+__global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const vlsa_bag_desc* __restrict__ bags, int B,
                                                                      const __bf16* __restrict__ qsplit,
                                                                      const __bf16* __restrict__ dsplit, int P,
                                                                      const float* __restrict__ m2, const float* __restrict__ l,
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
 
     unsigned char* ring = smem + w * kWaveRing;
     unsigned char* exch = smem + kRingBytes;
-    int_ma* tab = reinterpret_cast<int_ma*>(smem + kTabOff);
+    const StreamTab<kTabInts> tab{reinterpret_cast<int_ma*>(smem + kTabOff)};
     const bool pok = i16 < P;
     // compact exchange slot of query p = i16 inside its g block, rotated by 4 g: ds_read_b128 is serviced in the lane groups
     // {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... and without the rotation the g and g + 1 parts of a group share banks
@@ -109,28 +89,10 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
 
     // ---- bag table: thread t describes this workgroup's rows of bag t -------------------------------------------
     if (tid < B) {
-        const BagDesc d = bags[tid];
-        // 64-row units (= one lock-step iteration of the two row groups); the workgroup that gets the remainder
-        // unit rotates with the bag index so that the extra iterations even out over the batch
-        const unsigned long long units = (unsigned long long)((d.N + 31) >> 5);
-        const unsigned int uq = (unsigned int)(units / (unsigned int)G), ur = (unsigned int)(units % (unsigned int)G);
+        const vlsa_bag_desc d = bags[tid];
+        // 32-row units (= one tile of the workgroup's four waves); the bags of another workgroup group get an empty range
         const unsigned int vb = (unsigned int)((b + (tid / S) * 37) % G);  // virtual workgroup index for this bag
-        const bool mine = (tid % S) == grp;
-        const unsigned long long ubeg = (unsigned long long)vb * uq + (vb < ur ? vb : ur);
-        const long long rbeg = (long long)(ubeg << 5);
-        long long rend = (long long)((ubeg + uq + (vb < ur ? 1u : 0u)) << 5);
-        if (rend > d.N) rend = d.N;
-        const int nrows = (mine && rend > rbeg) ? (int)(rend - rbeg) : 0;
-        const unsigned long long addr = reinterpret_cast<unsigned long long>(d.X) + (unsigned long long)rbeg * d.ldx * 2ull;
-        int_ma* e = tab + tid * 8;
-        e[0] = (int)(unsigned int)addr;
-        e[1] = (int)((addr >> 32) & 0xffffu);
-        e[2] = nrows > 0 ? (int)(((long long)(nrows - 1) * d.ldx + D) * 2) : 0;  // descriptor span in bytes
-        e[3] = (int)(d.ldx * 2);                                                    // row pitch in bytes
-        e[4] = nrows;
-        e[5] = (nrows + kTile - 1) / kTile;
-        e[6] = (int)vb;  // partial slot of this workgroup for this bag
-        e[7] = mine ? 1 : 0;
+        stream_split<5, 2, kTile>(d, G, vb, (tid % S) == grp, tab.entry(tid));
     }
     // query B-fragments (scale * log2 e folded in): lane holds Q[p = i16][128 cw + 32 kk + 8 g .. +8]
     bf16x8 qf[3][4];
@@ -146,60 +108,15 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    auto tab_get = [&](int bag, int k) -> int { return __builtin_amdgcn_readfirstlane(tab[bag * 8 + k]); };
-
-    const unsigned int ring_lds = (unsigned int)(uintptr_t)(lds_void_ptr)ring;
-    const int lr = lane >> 4;
-    const int chunk_e = ((lane & 15) ^ (lr << 1)) << 4, chunk_o = ((lane & 15) ^ (lr << 1) ^ 8) << 4;
-    // LDS-DMA of one 32-row tile of `bag` into ring slot `slot` (see k_vlfan_partial_dma for the layout)
-    // descriptor of the bag the DMA currently streams from, cached in SGPRs (reloaded from the table on a bag change)
-    int ib = -1, ildb = 0, voff_e = 0, voff_o = 0;
-    i32x4 rsrc = {0, 0, 0, 0x00020000};
-    auto issue_tile = [&](int bag, int tile, int slot) {
-        if (bag != ib) {
-            const int4 e = *reinterpret_cast<const int4*>(smem + kTabOff + bag * 32);
-            rsrc[0] = __builtin_amdgcn_readfirstlane(e.x);
-            rsrc[1] = __builtin_amdgcn_readfirstlane(e.y);
-            rsrc[2] = __builtin_amdgcn_readfirstlane(e.z);
-            ildb = __builtin_amdgcn_readfirstlane(e.w);
-            voff_e = lr * ildb + cw * 256 + chunk_e;
-            voff_o = lr * ildb + cw * 256 + chunk_o;
-            ib = bag;
-        }
-        const int ldb = ildb;
-        const int sbase = tile * kTile * ldb;
-        const unsigned int dst = ring_lds + slot * kSlot;
-        unsigned int keep;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %1\n\t"
-                "s_nop 0\n\t"
-                "buffer_load_dwordx4 %2, %3, %4 offen " VLSA_DMA_NT " lds\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "s"(dst + i * 1024), "v"((i & 1) ? voff_o : voff_e), "s"(rsrc), "s"(sbase + i * 4 * ldb)
-                : "memory");
-        }
-    };
-    // this row group's next own tile after (bag, tile): same bag if it has one, else the first of a later bag
-    auto next_of = [&](int bag, int tile, int ntiles_bag, int& nb, int& nt) {
-        if (tile + 1 < ntiles_bag) {
-            nb = bag;
-            nt = tile + 1;
-            return;
-        }
-        nb = bag + 1;
-        while (nb < B && tab_get(nb, 5) <= 0) ++nb;
-        nt = 0;
-    };
+    DmaRingBf16 dma(ring, lane, cw);  // LDS-DMA of one 32-row tile into a ring slot (vlfan_stream.h)
 
     int kown = 0;      // own tiles consumed so far by this wave; own tile k lives in ring slot k & 1
     {
-        int fb = 0;  // first own tile of the whole batch
-        while (fb < B && tab_get(fb, 5) <= 0) ++fb;
-        if (fb < B) issue_tile(fb, 0, 0);
+        const int fb = stream_first_bag(tab, 0, B, 0);  // first own tile of the whole batch
+        if (fb < B) {
+            dma.bind(tab.entry(fb), fb);
+            dma.issue(0, 0);
+        }
     }
 
     
@@ -208,8 +125,8 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
     for (int ct = 0; ct < 8; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int bag = 0; bag < B; ++bag) {
-        if (tab_get(bag, 7) == 0) continue;  // another group's bag (workgroup-uniform)
-        const int nrows = tab_get(bag, 4), ntiles = tab_get(bag, 5);
+        if (tab.get(bag, kEntMine) == 0) continue;  // another group's bag (workgroup-uniform)
+        const int nrows = tab.get(bag, kEntRows), ntiles = tab.get(bag, kEntTiles);
         const int niter = ntiles;
         if (niter == 0) continue;
         // per-bag upstream gradient: dout fragments (same layout as the query fragments), m2, 1/l, delta
@@ -244,10 +161,11 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
             }
             if (have) {
                 int nb, nt;
-                next_of(bag, tile, ntiles, nb, nt);
+                stream_next<1>(tab, bag, tile, ntiles, B, 0, nb, nt);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of slot^1's old contents have returned
                 if (nb < B) {
-                    issue_tile(nb, nt, slot ^ 1);
+                    dma.bind(tab.entry(nb), nb);
+                    dma.issue(nt, slot ^ 1);
                     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // this tile landed; the next 8 pieces stay in flight
                 } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -257,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
                     for (int kk = 0; kk < 4; ++kk)
-                        xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + wswz(16 * h + i16, kk * 64 + g * 16));
+                        xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + swz(16 * h + i16, kk * 64 + g * 16));
                 __builtin_amdgcn_sched_barrier(0);
                 f32x4 Sb[2], Db[2];
                 Sb[0] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -281,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
                 Dd[1] += Db[1];
             }
 
-            VLSA_WBAR();  // readers of the previous exchange are done
+            VLSA_LDS_BARRIER();  // readers of the previous exchange are done
             {
                 unsigned char* mine = exch + cw * kExchWave;
                 if (i16 < kMaxP) {  // compact tiles: [h][g][p < 12] x f32x4
@@ -298,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
                     reinterpret_cast<float_ma*>(mine + 2 * kTileBytes)[16 + i16] = d1;
                 }
             }
-            VLSA_WBAR();
+            VLSA_LDS_BARRIER();
             if (have) {
                 f32x4 T[2], DA[2], R2[2];
                 {
@@ -337,8 +255,8 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_dma_batch(const BagDe
                 for (int ct = 0; ct < 8; ++ct) {
                     const int c_off = ct * 32 + (i16 & 3) * 8;
                     const int rr = 4 * g + (i16 >> 2);
-                    const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + wswz(rr, c_off)));
-                    const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + wswz(16 + rr, c_off)));
+                    const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(rr, c_off)));
+                    const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(16 + rr, c_off)));
                     const bf16x8 bh = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                     acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bh, acc[ct], 0, 0, 0);
                     acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[ct], 0, 0, 0);
@@ -380,32 +298,48 @@ extern "C" int vlsa_bwd_batch_partials(void) { return 512; }
 
 extern "C" size_t vlsa_bwd_batch_prep_bytes(int B, int D) { return (size_t)B * 3 * 16 * D * 2 + (size_t)B * kPStride * 4; }
 
+// What both batched backward entry points do first: check the arguments, carve bwd_prep into dsplit [B][3][16][D] bf16 and
+// delta [B][16], fill them (k_prepare_backward_batch) and find the prepared queries' bf16 split.  bf16_max_p: the most queries the
+// caller's kernel takes with bf16 bags.
+static int backward_prepare(const void* bag_desc, int B, int x_dtype, int D, const void* qprep, int P, int bf16_max_p, const float* dout,
+                            const float* out, const float* m2, const float* l, void* bwd_prep, const float* pm, const float* pl,
+                            const float* pacc, hipStream_t s, const __bf16** qsplit, const __bf16** dsplit, const float** delta) {
+    if (!bag_desc || !qprep || !dout || !out || !m2 || !l || !bwd_prep || !pm || !pl || !pacc) return VLSA_EINVAL;
+    if (B < 1 || B > bb::kMaxBags || P < 1 || P > VLSA_MAX_P) return VLSA_EINVAL;
+    if (D != 512 || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
+    if (x_dtype == VLSA_DT_BF16 && P > bf16_max_p) return VLSA_EUNSUPPORTED;
+    __bf16* ds = static_cast<__bf16*>(bwd_prep);
+    float* dl = reinterpret_cast<float*>(static_cast<unsigned char*>(bwd_prep) + (size_t)B * 3 * 16 * D * 2);
+    hipLaunchKernelGGL(k_prepare_backward_batch, dim3(16, B), dim3(256), 0, s, dout, out, P, D, ds, dl);
+    *qsplit = reinterpret_cast<const __bf16*>(static_cast<const unsigned char*>(qprep) + QPrepLayout(D).qsplit);
+    *dsplit = ds;
+    *delta = dl;
+    return VLSA_OK;
+}
+
 extern "C" int vlsa_vlfan_backward_batch(const void* bag_desc, int B, int x_dtype, int D, const void* qprep, int P,
                                          float coattn_scale, const float* dout, const float* out, const float* m2,
                                          const float* l, void* bwd_prep, float* pm, float* pl, float* pacc, int groups,
                                          void* stream) {
-    if (!bag_desc || !qprep || !dout || !out || !m2 || !l || !bwd_prep || !pm || !pl || !pacc) return VLSA_EINVAL;
-    if (B < 1 || B > bb::kMaxBags || P < 1 || P > VLSA_MAX_P) return VLSA_EINVAL;
-    if (D != 512 || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
-    if (x_dtype == VLSA_DT_BF16 && P > bb::kMaxP) return VLSA_EUNSUPPORTED;   // (fp32 bags: any P <= 16)
+    hipStream_t s = (hipStream_t)stream;
+    const __bf16 *qsplit, *dsplit;
+    const float* delta;
+    // the compact exchange takes P <= 12 with bf16 bags (fp32 bags: any P <= 16)
+    const int rc = backward_prepare(bag_desc, B, x_dtype, D, qprep, P, bb::kMaxP, dout, out, m2, l, bwd_prep, pm, pl, pacc, s, &qsplit, &dsplit,
+                                    &delta);
+    if (rc != VLSA_OK) return rc;
     int S = groups > 0 ? groups : bwd_groups(B);  // bags in flight: power of two <= min(B, 64)
     {
         int p2 = 1;
         while (p2 * 2 <= S && p2 * 2 <= B && p2 * 2 <= 64) p2 *= 2;
         S = p2;
     }
-    hipStream_t s = (hipStream_t)stream;
-    __bf16* dsplit = static_cast<__bf16*>(bwd_prep);
-    float* delta = reinterpret_cast<float*>(static_cast<unsigned char*>(bwd_prep) + (size_t)B * 3 * 16 * D * 2);
-    hipLaunchKernelGGL(k_prepare_backward_batch, dim3(16, B), dim3(256), 0, s, dout, out, P, D, dsplit, delta);
-    const QPrepLayout L(D);
-    const __bf16* qsplit = reinterpret_cast<const __bf16*>(static_cast<const unsigned char*>(qprep) + L.qsplit);
     if (x_dtype == VLSA_DT_F32)
         return vlsa_launch_backward_f32_batch(bag_desc, B, qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, S, s);
     static DeviceOnce attr_once;
     if (attr_once.first())
         (void)hipFuncSetAttribute((const void*)k_vlfan_backward_dma_batch, hipFuncAttributeMaxDynamicSharedMemorySize, bb::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_backward_dma_batch, dim3(512), dim3(256), bb::kLdsBytes, s, static_cast<const BagDesc*>(bag_desc), B,
+    hipLaunchKernelGGL(k_vlfan_backward_dma_batch, dim3(512), dim3(256), bb::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
                        qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, S);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
@@ -414,21 +348,19 @@ int vlsa_launch_backward_mfma_bags(const void* bag_desc, int B, int x_dtype, con
                                    const float* m2, const float* l, const float* delta, float scale, float* pm, float* pl,
                                    float* pacc, int G, hipStream_t s);  // vlfan_backward.hip
 
-/* The same backward for batches the persistent kernel does not take (fp32 bags, P > 12): the per-bag kernel of
- * vlfan_backward.hip over the bag table in ONE launch, grid (G, B) -- G row blocks per bag (the caller passes the largest
- * vlsa_num_partials(N_i) of the batch); B * G partial sums in pm (= 0), pl (= 1) [B * G, 16], pacc [B * G, P, D], to be reduced
- * with vlsa_vlfan_merge(..., B * G, normalise = 0).  bwd_prep: vlsa_bwd_batch_prep_bytes(B, D). */
+/* The same backward for batches the persistent kernel does not take (bf16 bags with P > 12) or at a caller-chosen number of row
+ * blocks: the per-bag kernel of vlfan_backward.hip over the bag table in ONE launch, grid (G, B) -- G row blocks per bag (the
+ * caller passes the largest vlsa_num_partials(N_i) of the batch); B * G partial sums in pm (= 0), pl (= 1) [B * G, 16],
+ * pacc [B * G, P, D], to be reduced with vlsa_vlfan_merge(..., B * G, normalise = 0).  bwd_prep: vlsa_bwd_batch_prep_bytes(B, D). */
 extern "C" int vlsa_vlfan_backward_bags(const void* bag_desc, int B, int x_dtype, int D, const void* qprep, int P,
                                         float coattn_scale, const float* dout, const float* out, const float* m2, const float* l,
                                         void* bwd_prep, float* pm, float* pl, float* pacc, int G, void* stream) {
-    if (!bag_desc || !qprep || !dout || !out || !m2 || !l || !bwd_prep || !pm || !pl || !pacc) return VLSA_EINVAL;
-    if (B < 1 || B > bb::kMaxBags || P < 1 || P > VLSA_MAX_P || G < 1) return VLSA_EINVAL;
-    if (D != 512 || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
+    if (G < 1) return VLSA_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    __bf16* dsplit = static_cast<__bf16*>(bwd_prep);
-    float* delta = reinterpret_cast<float*>(static_cast<unsigned char*>(bwd_prep) + (size_t)B * 3 * 16 * D * 2);
-    hipLaunchKernelGGL(k_prepare_backward_batch, dim3(16, B), dim3(256), 0, s, dout, out, P, D, dsplit, delta);
-    const QPrepLayout L(D);
-    const __bf16* qsplit = reinterpret_cast<const __bf16*>(static_cast<const unsigned char*>(qprep) + L.qsplit);
+    const __bf16 *qsplit, *dsplit;
+    const float* delta;
+    const int rc = backward_prepare(bag_desc, B, x_dtype, D, qprep, P, VLSA_MAX_P, dout, out, m2, l, bwd_prep, pm, pl, pacc, s, &qsplit, &dsplit,
+                                    &delta);
+    if (rc != VLSA_OK) return rc;
     return vlsa_launch_backward_mfma_bags(bag_desc, B, x_dtype, qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, G, s);
 }

@@ -15,22 +15,10 @@
 // unlike the forward -- whose exact f32 scores define the attention weights it hands out -- the backward only needs
 // A = exp2(t - m2) / l to the gradient tolerance, and the 2^-17 operand split moves t by ~3e-5.
 // No P <= 12 restriction here (the exchange tiles are the full 16 x 16).
-#include "vlsa_common.h"
+#define VLSA_STREAM_NT "nt"
+#include "vlfan_stream.h"
 
 namespace vlsa {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr_bf;
-typedef f32x4 __attribute__((may_alias)) f32x4_mbf;
-typedef float __attribute__((may_alias)) float_mbf;
-typedef int __attribute__((may_alias)) int_mbf;
-typedef int i32x4bf __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64bf __attribute__((may_alias));
-
-struct BagDescF {
-    const void* X;
-    int64_t N;
-    int64_t ldx;
-};
 
 namespace bbf {
 constexpr int kTile = 16;                        // rows per tile
@@ -40,21 +28,12 @@ constexpr int kRingBytes = 4 * kWaveRing;        // 64 KiB: four waves
 constexpr int kExchWave = 2 * 1024 + 64;         // S tile + dA tile (one f32x4 per lane each) + 16 row sums of squares
 constexpr int kExchBytes = 4 * kExchWave;
 constexpr int kTabOff = kRingBytes + kExchBytes;
+constexpr int kTabInts = 8;                      // the stream-descriptor ints
 constexpr int kMaxBags = 64;
-constexpr int kLdsBytes = kTabOff + kMaxBags * 32;   // 76,032 B: two workgroups per CU
+constexpr int kLdsBytes = kTabOff + kMaxBags * kTabInts * 4;   // 76,032 B: two workgroups per CU
 }  // namespace bbf
 
-// element (row, col) of a wave's fp32 slice image (see vlfan_batch_f32.hip)
-__device__ __forceinline__ int fswzb(int row, int col) { return row * 512 + ((((col >> 2) ^ (row & 15))) << 4) + ((col & 3) << 2); }
-
-#define VLSA_FBBAR()                                         \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-    } while (0)
-
-__global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDescF* __restrict__ bags, int B,
+__global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const vlsa_bag_desc* __restrict__ bags, int B,
                                                                      const __bf16* __restrict__ qsplit,
                                                                      const __bf16* __restrict__ dsplit, int P,
                                                                      const float* __restrict__ m2, const float* __restrict__ l,
@@ -72,31 +51,14 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
 
     unsigned char* ring = smem + cw * kWaveRing;
     unsigned char* exch = smem + kRingBytes;
-    int_mbf* tab = reinterpret_cast<int_mbf*>(smem + kTabOff);
+    const StreamTab<kTabInts> tab{reinterpret_cast<int_ma*>(smem + kTabOff)};
     const bool pok = i16 < P;
 
     // ---- bag table: thread t describes this workgroup's rows of bag t (16-row units) ------------------------------
     if (tid < B) {
-        const BagDescF d = bags[tid];
-        const unsigned long long units = (unsigned long long)((d.N + 15) >> 4);
-        const unsigned int uq = (unsigned int)(units / (unsigned int)G), ur = (unsigned int)(units % (unsigned int)G);
+        const vlsa_bag_desc d = bags[tid];
         const unsigned int vb = (unsigned int)((b + (tid / S) * 37) % G);  // virtual workgroup index for this bag
-        const bool mine = (tid % S) == grp;
-        const unsigned long long ubeg = (unsigned long long)vb * uq + (vb < ur ? vb : ur);
-        const long long rbeg = (long long)(ubeg << 4);
-        long long rend = (long long)((ubeg + uq + (vb < ur ? 1u : 0u)) << 4);
-        if (rend > d.N) rend = d.N;
-        const int nrows = (mine && rend > rbeg) ? (int)(rend - rbeg) : 0;
-        const unsigned long long addr = reinterpret_cast<unsigned long long>(d.X) + (unsigned long long)rbeg * d.ldx * 4ull;
-        int_mbf* e = tab + tid * 8;
-        e[0] = (int)(unsigned int)addr;
-        e[1] = (int)((addr >> 32) & 0xffffu);
-        e[2] = nrows > 0 ? (int)(((long long)(nrows - 1) * d.ldx + D) * 4) : 0;  // descriptor span in bytes
-        e[3] = (int)(d.ldx * 4);                                                    // row pitch in bytes
-        e[4] = nrows;
-        e[5] = (nrows + kTile - 1) / kTile;
-        e[6] = 0;
-        e[7] = mine ? 1 : 0;
+        stream_split<4, 4, kTile>(d, G, vb, (tid % S) == grp, tab.entry(tid));
     }
     // query fragments: the 3-term bf16 split of the effective queries (scale * log2 e folded in), in the column map of the row
     // fragments: k-slot e of lane group g of step s <-> column 128 cw + 32 s + 16 (e >> 2) + 4 g + (e & 3)
@@ -116,57 +78,15 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    auto tab_get = [&](int bag, int k) -> int { return __builtin_amdgcn_readfirstlane(tab[bag * 8 + k]); };
-
-    const unsigned int ring_lds = (unsigned int)(uintptr_t)(lds_void_ptr_bf)ring;
-    const int lr = lane >> 5, lc = lane & 31;
-    int ib = -1, ildb = 0;
-    int voff[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // row of piece i within the tile is 2 i + lr
-    i32x4bf rsrc = {0, 0, 0, 0x00020000};
-    auto issue_tile = [&](int bag, int tile, int slot) {
-        if (bag != ib) {
-            const int4 e = *reinterpret_cast<const int4*>(smem + kTabOff + bag * 32);
-            rsrc[0] = __builtin_amdgcn_readfirstlane(e.x);
-            rsrc[1] = __builtin_amdgcn_readfirstlane(e.y);
-            rsrc[2] = __builtin_amdgcn_readfirstlane(e.z);
-            ildb = __builtin_amdgcn_readfirstlane(e.w);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) voff[q] = lr * ildb + cw * 512 + ((lc ^ (2 * q + lr)) << 4);
-            ib = bag;
-        }
-        const int ldb = ildb;
-        const int sbase = tile * kTile * ldb;
-        const unsigned int dst = ring_lds + slot * kSlot;
-        unsigned int keep;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %1\n\t"
-                "s_nop 0\n\t"
-                "buffer_load_dwordx4 %2, %3, %4 offen nt lds\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "s"(dst + i * 1024), "v"(voff[i]), "s"(rsrc), "s"(sbase + i * 2 * ldb)
-                : "memory");
-        }
-    };
-    auto next_of = [&](int bag, int tile, int ntiles_bag, int& nb, int& nt) {
-        if (tile + 1 < ntiles_bag) {
-            nb = bag;
-            nt = tile + 1;
-            return;
-        }
-        nb = bag + 1;
-        while (nb < B && tab_get(nb, 5) <= 0) ++nb;
-        nt = 0;
-    };
+    DmaRingF32 dma(ring, lane, cw);  // LDS-DMA of one 16-row tile into a ring slot (vlfan_stream.h)
 
     int kown = 0;      // tiles consumed so far by this wave; tile k lives in ring slot k & 1
     {
-        int fb = 0;
-        while (fb < B && tab_get(fb, 5) <= 0) ++fb;
-        if (fb < B) issue_tile(fb, 0, 0);
+        const int fb = stream_first_bag(tab, 0, B, 0);  // first own tile of the whole batch
+        if (fb < B) {
+            dma.bind(tab.entry(fb), fb);
+            dma.issue(0, 0);
+        }
     }
 
     f32x4 acc[8];
@@ -174,8 +94,8 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
     for (int ct = 0; ct < 8; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int bag = 0; bag < B; ++bag) {
-        if (tab_get(bag, 7) == 0) continue;  // another group's bag (workgroup-uniform)
-        const int nrows = tab_get(bag, 4), ntiles = tab_get(bag, 5);
+        if (tab.get(bag, kEntMine) == 0) continue;  // another group's bag (workgroup-uniform)
+        const int nrows = tab.get(bag, kEntRows), ntiles = tab.get(bag, kEntTiles);
         if (ntiles == 0) continue;
         // per-bag upstream gradient: dout fragments (hi + lo bf16, the column map of the score fragments), m2, 1/l, delta
         bf16x8 df[2][4];
@@ -204,10 +124,11 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
             float ss = 0.f;
             {
                 int nb, nt;
-                next_of(bag, tile, ntiles, nb, nt);
+                stream_next<1>(tab, bag, tile, ntiles, B, 0, nb, nt);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of slot^1's old contents have returned
                 if (nb < B) {
-                    issue_tile(nb, nt, slot ^ 1);
+                    dma.bind(tab.entry(nb), nb);
+                    dma.issue(nt, slot ^ 1);
                     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // this tile landed; the next 8 pieces stay in flight
                 } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -215,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
                 float xa[32];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const f32x4 v = *reinterpret_cast<const f32x4_mbf*>(xs + fswzb(i16, 16 * j + 4 * g));
+                    const f32x4 v = *reinterpret_cast<const f32x4_ma*>(xs + fswz(i16, 16 * j + 4 * g));
                     xa[4 * j] = v[0];
                     xa[4 * j + 1] = v[1];
                     xa[4 * j + 2] = v[2];
@@ -253,14 +174,14 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
                 Dv += Db;
             }
 
-            VLSA_FBBAR();  // readers of the previous exchange are done
+            VLSA_LDS_BARRIER();  // readers of the previous exchange are done
             {
                 unsigned char* mine = exch + cw * kExchWave;
-                *reinterpret_cast<f32x4_mbf*>(mine + lane * 16) = Sv;
-                *reinterpret_cast<f32x4_mbf*>(mine + 1024 + lane * 16) = Dv;
-                if (g == 0) reinterpret_cast<float_mbf*>(mine + 2048)[i16] = ss;
+                *reinterpret_cast<f32x4_ma*>(mine + lane * 16) = Sv;
+                *reinterpret_cast<f32x4_ma*>(mine + 1024 + lane * 16) = Dv;
+                if (g == 0) reinterpret_cast<float_ma*>(mine + 2048)[i16] = ss;
             }
-            VLSA_FBBAR();
+            VLSA_LDS_BARRIER();
             {
                 f32x4 T, DA, R2;
                 {
@@ -268,9 +189,9 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
 #pragma unroll
                     for (int ww = 0; ww < 4; ++ww) {
                         const unsigned char* o = exch + ww * kExchWave;
-                        tv[ww] = *reinterpret_cast<const f32x4_mbf*>(o + lane * 16);
-                        dv[ww] = *reinterpret_cast<const f32x4_mbf*>(o + 1024 + lane * 16);
-                        rv[ww] = *reinterpret_cast<const f32x4_mbf*>(o + 2048 + 16 * g);
+                        tv[ww] = *reinterpret_cast<const f32x4_ma*>(o + lane * 16);
+                        dv[ww] = *reinterpret_cast<const f32x4_ma*>(o + 1024 + lane * 16);
+                        rv[ww] = *reinterpret_cast<const f32x4_ma*>(o + 2048 + 16 * g);
                     }
                     T = (tv[0] + tv[1]) + (tv[2] + tv[3]);
                     DA = (dv[0] + dv[1]) + (dv[2] + dv[3]);
@@ -289,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void k_vlfan_backward_f32_batch(const BagDe
 #pragma unroll
                 for (int rs = 0; rs < 4; ++rs)
 #pragma unroll
-                    for (int ct = 0; ct < 8; ++ct) xb[rs][ct] = *reinterpret_cast<const float_mbf*>(xs + fswzb(4 * g + rs, 16 * ct + i16));
+                    for (int ct = 0; ct < 8; ++ct) xb[rs][ct] = *reinterpret_cast<const float_ma*>(xs + fswz(4 * g + rs, 16 * ct + i16));
                 bf16x4 uhi, ulo;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -342,7 +263,7 @@ int vlsa_launch_backward_f32_batch(const void* bag_desc, int B, const __bf16* qs
     static DeviceOnce attr_once;
     if (attr_once.first())
         (void)hipFuncSetAttribute((const void*)k_vlfan_backward_f32_batch, hipFuncAttributeMaxDynamicSharedMemorySize, bbf::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_backward_f32_batch, dim3(512), dim3(256), bbf::kLdsBytes, s, static_cast<const BagDescF*>(bag_desc), B,
+    hipLaunchKernelGGL(k_vlfan_backward_f32_batch, dim3(512), dim3(256), bbf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
                        qsplit, dsplit, P, m2, l, delta, scale, pm, pl, pacc, S);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }

@@ -12,29 +12,13 @@
 // synchronisation differs: counted s_waitcnt vmcnt(N) keeps the next tile's DMA in flight as there, but the two row groups
 // run one raw s_barrier apart, so the two waves of a SIMD alternate between the matrix-heavy and the latency-bound half of
 // an iteration instead of doing the same half at the same time (the tile loop below).
-#include "vlsa_common.h"
 #ifndef VLSA_DMA_NT
 #define VLSA_DMA_NT "nt"      // streaming rows: non-temporal (measurement builds may pass -DVLSA_DMA_NT=\"\")
 #endif
+#define VLSA_STREAM_NT VLSA_DMA_NT
+#include "vlfan_stream.h"
 
 namespace vlsa {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef bf16x8 __attribute__((may_alias)) bf16x8_ma;
-typedef f32x4 __attribute__((may_alias)) f32x4_ma;
-typedef float __attribute__((may_alias)) float_ma;
-typedef int __attribute__((may_alias)) int_ma;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-struct BagDesc {  // device-side description of one bag (mirrors vlsa_bag_desc in vlsa_hip.h)
-    const void* X;
-    int64_t N;
-    int64_t ldx;
-};
-struct RowsDesc {  // one [P, ld] fp32 matrix per bag (mirrors vlsa_rows_desc in vlsa_hip.h)
-    float* ptr;
-    int64_t ld;
-};
 
 #ifdef VLSA_TIMING
 __device__ long long vlsa_dbg_batch[64];
@@ -75,15 +59,6 @@ constexpr int kLdsBytes = kMlOff + 8 * 32 * 4;        // 152,576 B
 constexpr float kThr = 16.0f;
 }  // namespace bt
 
-__device__ __forceinline__ int bswz(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
-
-#define VLSA_BAR()                                           \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-    } while (0)
-
 // S = number of workgroup groups: bag t is streamed by the Gb = G / S workgroups of group t % S only, so S bags are in
 // flight at once, every workgroup sees S times more rows per bag (fewer bag epilogues, better tile quantisation) and a
 // bag leaves Gb instead of G partials behind.
@@ -91,11 +66,11 @@ __device__ __forceinline__ int bswz(int row, int byte_off) { return row * 256 + 
 // pointer ([P, ld] fp32 per bag, ld % 4 == 0, ld >= N rounded up to 64) -- the raw material of the attention weights
 // A = softmax_N (model/deepmil.py:198,206-215), which need the bag-global (m, l) and are finished by k_attn_normalise_batch.
 template <bool kScores>
-__global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDesc* __restrict__ bags, int B,
+__global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const vlsa_bag_desc* __restrict__ bags, int B,
                                                                      const __bf16* __restrict__ qsplit, int P,
                                                                      float* __restrict__ pm, float* __restrict__ pl,
                                                                      float* __restrict__ pacc, int S,
-                                                                     const RowsDesc* __restrict__ sdesc) {
+                                                                     const vlsa_rows_desc* __restrict__ sdesc) {
     using namespace bt;
     constexpr int D = 512;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -114,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
 
     unsigned char* ring = smem + w * kWaveRing;
     unsigned char* exch = smem + kRingBytes + rg * kExchGroup;
-    int_ma* tab = reinterpret_cast<int_ma*>(smem + kTabOff);
+    const StreamTab<kTabInts> tab{reinterpret_cast<int_ma*>(smem + kTabOff)};
 
     // ---- bag table: the workgroup streams the bags grp, grp + S, grp + 2 S, ... only, so the LDS table holds THOSE bags
     // (local index lb <-> bag grp + lb * S: at most kMaxLocal entries whatever B is); thread lb describes this workgroup's
@@ -122,35 +97,18 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
     const int nloc = grp < B ? (B - grp + S - 1) / S : 0;
     if (tid < nloc) {
         const int bag_id = grp + tid * S;
-        const BagDesc d = bags[bag_id];
-        // 64-row units (= one lock-step iteration of the two row groups); the workgroup that gets the remainder
-        // unit rotates with the bag index so that the extra iterations even out over the batch
-        const unsigned long long units = (unsigned long long)((d.N + 63) >> 6);
-        const unsigned int uq = (unsigned int)(units / (unsigned int)G), ur = (unsigned int)(units % (unsigned int)G);
+        const vlsa_bag_desc d = bags[bag_id];
+        // 64-row units (= one lock-step iteration of the two row groups)
         const unsigned int vb = (unsigned int)((b + tid * 37) % G);  // virtual workgroup index for this bag
-        constexpr bool mine = true;
-        const unsigned long long ubeg = (unsigned long long)vb * uq + (vb < ur ? vb : ur);
-        const long long rbeg = (long long)(ubeg << 6);
-        long long rend = (long long)((ubeg + uq + (vb < ur ? 1u : 0u)) << 6);
-        if (rend > d.N) rend = d.N;
-        const int nrows = (mine && rend > rbeg) ? (int)(rend - rbeg) : 0;
-        const unsigned long long addr = reinterpret_cast<unsigned long long>(d.X) + (unsigned long long)rbeg * d.ldx * 2ull;
-        int_ma* e = tab + tid * kTabInts;
+        int_ma* e = tab.entry(tid);
+        const long long rbeg = stream_split<6, 2, kTile>(d, G, vb, true, e);
         if constexpr (kScores) {
-            const RowsDesc sd = sdesc[bag_id];
+            const vlsa_rows_desc sd = sdesc[bag_id];
             const unsigned long long sp = sd.ptr ? reinterpret_cast<unsigned long long>(sd.ptr + rbeg) : 0ull;
-            e[8] = (int)(unsigned int)sp;
-            e[9] = (int)(sp >> 32);
-            e[10] = (int)sd.ld;
+            e[kEntScoreLo] = (int)(unsigned int)sp;
+            e[kEntScoreHi] = (int)(sp >> 32);
+            e[kEntScorePitch] = (int)sd.ld;
         }
-        e[0] = (int)(unsigned int)addr;
-        e[1] = (int)((addr >> 32) & 0xffffu);
-        e[2] = nrows > 0 ? (int)(((long long)(nrows - 1) * d.ldx + D) * 2) : 0;  // descriptor span in bytes
-        e[3] = (int)(d.ldx * 2);                                                    // row pitch in bytes
-        e[4] = nrows;
-        e[5] = (nrows + kTile - 1) / kTile;
-        e[6] = (int)vb;  // partial slot of this workgroup for this bag
-        e[7] = mine ? 1 : 0;
     }
     // query B-fragments (scale * log2 e folded in): lane holds Q[p = i16][128 cw + 32 kk + 8 g .. +8]
     bf16x8 qf[3][4];
@@ -166,67 +124,22 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    auto tab_get = [&](int bag, int k) -> int { return __builtin_amdgcn_readfirstlane(tab[bag * kTabInts + k]); };
-
-    const unsigned int ring_lds = (unsigned int)(uintptr_t)(lds_void_ptr)ring;
-    const int lr = lane >> 4;
-    const int chunk_e = ((lane & 15) ^ (lr << 1)) << 4, chunk_o = ((lane & 15) ^ (lr << 1) ^ 8) << 4;
-    // LDS-DMA of one 32-row tile of `bag` into ring slot `slot` (see k_vlfan_partial_dma for the layout)
-    // descriptor of the bag the DMA currently streams from, cached in SGPRs (reloaded from the table on a bag change)
-    int ib = -1, ildb = 0, voff_e = 0, voff_o = 0;
-    i32x4 rsrc = {0, 0, 0, 0x00020000};
-    auto issue_tile = [&](int bag, int tile, int slot) {
-        if (bag != ib) {
-            const int4 e = *reinterpret_cast<const int4*>(smem + kTabOff + bag * (kTabInts * 4));
-            rsrc[0] = __builtin_amdgcn_readfirstlane(e.x);
-            rsrc[1] = __builtin_amdgcn_readfirstlane(e.y);
-            rsrc[2] = __builtin_amdgcn_readfirstlane(e.z);
-            ildb = __builtin_amdgcn_readfirstlane(e.w);
-            voff_e = lr * ildb + cw * 256 + chunk_e;
-            voff_o = lr * ildb + cw * 256 + chunk_o;
-            ib = bag;
-        }
-        const int ldb = ildb;
-        const int sbase = tile * kTile * ldb;
-        const unsigned int dst = ring_lds + slot * kSlot;
-        unsigned int keep;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %1\n\t"
-                "s_nop 0\n\t"
-                "buffer_load_dwordx4 %2, %3, %4 offen " VLSA_DMA_NT " lds\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "s"(dst + i * 1024), "v"((i & 1) ? voff_o : voff_e), "s"(rsrc), "s"(sbase + i * 4 * ldb)
-                : "memory");
-        }
-    };
-    // this row group's next own tile after (bag, tile): same bag if it has one, else the first of a later bag
-    auto next_of = [&](int bag, int tile, int ntiles_bag, int& nb, int& nt) {
-        if (tile + 2 < ntiles_bag) {
-            nb = bag;
-            nt = tile + 2;
-            return;
-        }
-        nb = bag + 1;
-        while (nb < nloc && tab_get(nb, 5) <= rg) ++nb;
-        nt = rg;
-    };
+    DmaRingBf16 dma(ring, lane, cw);  // LDS-DMA of one 32-row tile into a ring slot (vlfan_stream.h)
 
     int kown = 0;      // own tiles consumed so far by this wave; own tile k lives in ring slot k & 1
     int k0 = 0, k1 = 0;  // tiles consumed so far by row group 0 / 1 (for the epilogue's free-slot bookkeeping)
     {
-        int fb = 0;  // first own tile of the whole batch
-        while (fb < nloc && tab_get(fb, 5) <= rg) ++fb;
-        if (fb < nloc) issue_tile(fb, rg, 0);
+        const int fb = stream_first_bag(tab, 0, nloc, rg);  // first own tile of the whole batch
+        if (fb < nloc) {
+            dma.bind(tab.entry(fb), fb);
+            dma.issue(rg, 0);
+        }
     }
 
     int stamp = 0;
     BSTAMP(stamp++);
     for (int bag = 0; bag < nloc; ++bag) {   // `bag` = local index; the batch's bag index is grp + bag * S
-        const int nrows = tab_get(bag, 4), ntiles = tab_get(bag, 5);
+        const int nrows = tab.get(bag, kEntRows), ntiles = tab.get(bag, kEntTiles);
         const int niter = (ntiles + 1) >> 1;
         f32x4 acc[8];
 #pragma unroll
@@ -243,11 +156,11 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
         float* srow = nullptr;   // this lane's store address for tile row 0 of the workgroup's range
         bool has_scores = false; // wave-uniform: this bag stores scores and this wave is one of the two that do
         if constexpr (kScores) {
-            const unsigned long long sp = (unsigned long long)(unsigned int)tab_get(bag, 8) |
-                                          ((unsigned long long)(unsigned int)tab_get(bag, 9) << 32);
+            const unsigned long long sp = (unsigned long long)(unsigned int)tab.get(bag, kEntScoreLo) |
+                                          ((unsigned long long)(unsigned int)tab.get(bag, kEntScoreHi) << 32);
             const int sp_q = 8 * cw + (lane >> 3);
             has_scores = sp != 0 && cw < 2 && 8 * cw < P;
-            if (has_scores && sp_q < P) srow = reinterpret_cast<float*>(sp) + (size_t)sp_q * tab_get(bag, 10) + 4 * (lane & 7);
+            if (has_scores && sp_q < P) srow = reinterpret_cast<float*>(sp) + (size_t)sp_q * tab.get(bag, kEntScorePitch) + 4 * (lane & 7);
         }
 
         // Row group 1 runs ONE barrier behind row group 0: between two barriers a SIMD then pairs one group's phase (a) --
@@ -256,7 +169,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
         // window and both waves then waiting out the exchange / exp2 chain with the pipe idle.  Every barrier of the loop
         // still orders the exchange of the group for which it is the (a) -> (b) or (b) -> (a) boundary (each group has its
         // own exchange area and ring slots); both groups pass 2 niter + 1 barriers per bag and meet again in the epilogue.
-        if (rg == 1 && !(xmode & 2)) VLSA_BAR();
+        if (rg == 1 && !(xmode & 2)) VLSA_LDS_BARRIER();
         for (int it = 0; it < niter; ++it) {
             const int tile = 2 * it + rg;
             const bool have = tile < ntiles;  // wave-uniform
@@ -269,14 +182,15 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 S[h] = f32x4{0.f, 0.f, 0.f, 0.f};
                 Nd[h] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            if (!(xmode & 2)) VLSA_BAR();  // (b) -> (a): this group's readers of its previous exchange are done
+            if (!(xmode & 2)) VLSA_LDS_BARRIER();  // (b) -> (a): this group's readers of its previous exchange are done
             if (have) {
                 int nb, nt;
-                next_of(bag, tile, ntiles, nb, nt);
+                stream_next<2>(tab, bag, tile, ntiles, nloc, rg, nb, nt);
                 ISTAMP(0, 0.f);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of slot^1's old contents have returned
                 if (nb < nloc) {
-                    issue_tile(nb, nt, slot ^ 1);
+                    dma.bind(tab.entry(nb), nb);
+                    dma.issue(nt, slot ^ 1);
                     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // this tile landed; the next 8 pieces stay in flight
                 } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -287,7 +201,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
                     for (int kk = 0; kk < 4; ++kk)
-                        xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + bswz(16 * h + i16, kk * 64 + g * 16));
+                        xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + swz(16 * h + i16, kk * 64 + g * 16));
                 __builtin_amdgcn_sched_barrier(0);
                 f32x4 Sb[2];
                 Sb[0] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -320,7 +234,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 }
             }
             if (have) ISTAMP(3, 0.f);
-            if (!(xmode & 2)) VLSA_BAR();  // (a) -> (b): this group's exchange is written
+            if (!(xmode & 2)) VLSA_LDS_BARRIER();  // (a) -> (b): this group's exchange is written
             if (have) {
                 ISTAMP(4, 0.f);
                 f32x4 T[2], R2[2];
@@ -399,8 +313,8 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 for (int ct = 0; ct < 8; ++ct) {
                     const int c_off = ct * 32 + (i16 & 3) * 8;
                     const int rr = 4 * g + (i16 >> 2);
-                    const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + bswz(rr, c_off)));
-                    const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + bswz(16 + rr, c_off)));
+                    const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(rr, c_off)));
+                    const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(16 + rr, c_off)));
                     const bf16x8 bh = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                     acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bh, acc[ct], 0, 0, 0);
                     acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[ct], 0, 0, 0);
@@ -410,7 +324,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
             }
             BSTAMP(stamp++);
         }
-        if (rg == 0 && !(xmode & 2)) VLSA_BAR();  // row group 1's first barrier of the bag (above)
+        if (rg == 0 && !(xmode & 2)) VLSA_LDS_BARRIER();  // row group 1's first barrier of the bag (above)
         k0 += (ntiles + 1) >> 1;
         k1 += ntiles >> 1;
 
@@ -430,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
             mlw[w * 32 + i16] = M;
             mlw[w * 32 + 16 + i16] = lsum;
         }
-        VLSA_BAR();
+        VLSA_LDS_BARRIER();
         {
             const int wo = (rg ^ 1) * 4 + cw;
             // one round of LDS reads: both waves' reference maxima for the 4 queries of my accumulator rows, the
@@ -448,7 +362,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 am[r] = (Mm4[r] == -INFINITY) ? 0.f : fast_exp2(Mm4[r] - mn);
                 ao[r] = (Mo4[r] == -INFINITY) ? 0.f : fast_exp2(Mo4[r] - mn);
             }
-            const size_t slotg = (size_t)(grp + bag * S) * G + tab_get(bag, 6);
+            const size_t slotg = (size_t)(grp + bag * S) * G + tab.get(bag, kEntSlot);
             if (w == 0 && g == 0 && i16 < P) {
                 const float Mn = fmaxf(M, Mo);
                 const float fm = (M == -INFINITY) ? 0.f : fast_exp2(M - Mn);
@@ -472,7 +386,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma_batch(const BagDes
                 if (p < P) *reinterpret_cast<f32x4*>(dstp + (size_t)p * D) = v;
             }
         }
-        VLSA_BAR();  // lent slots and the transpose area are free again
+        VLSA_LDS_BARRIER();  // lent slots and the transpose area are free again
         BSTAMP(stamp++);
     }
 }
@@ -736,13 +650,13 @@ __global__ __launch_bounds__(256) void k_vlfan_merge_pool_small(const float* __r
 // A[p, n] = exp2(t[p, n] - m2[bag, p]) / l[bag, p] for every bag of a batch (softmax over the patches, model/deepmil.py:198),
 // from the scores the streaming kernel stored and the bag-global (m2, l) of the merge.  grid (chunks of 1024 patches, P, B);
 // float4 per thread; may run in place (A == scores).  Columns N .. ld-1 of a row hold -inf scores -> 0.
-__global__ __launch_bounds__(256) void k_attn_normalise_batch(const BagDesc* __restrict__ bags, const RowsDesc* __restrict__ sdesc,
-                                                             const RowsDesc* __restrict__ adesc, const float* __restrict__ m2,
+__global__ __launch_bounds__(256) void k_attn_normalise_batch(const vlsa_bag_desc* __restrict__ bags, const vlsa_rows_desc* __restrict__ sdesc,
+                                                             const vlsa_rows_desc* __restrict__ adesc, const float* __restrict__ m2,
                                                              const float* __restrict__ l, int m_stride) {
     const int bag = blockIdx.z, p = blockIdx.y;
     const int64_t n = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const int64_t N = bags[bag].N;
-    const RowsDesc sd = sdesc[bag], ad = adesc[bag];
+    const vlsa_rows_desc sd = sdesc[bag], ad = adesc[bag];
     if (n >= N || sd.ptr == nullptr || ad.ptr == nullptr) return;
     const float m = m2[(size_t)bag * m_stride + p], inv = 1.f / l[(size_t)bag * m_stride + p];
     const f32x4 t = *reinterpret_cast<const f32x4*>(sd.ptr + (size_t)p * sd.ld + n);
@@ -886,12 +800,12 @@ extern "C" int vlsa_vlfan_partial_batch_scores(const void* bag_desc, int B, int 
 #endif
     if (scores_desc)
         hipLaunchKernelGGL(k_vlfan_partial_dma_batch<true>, dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
-                           static_cast<const BagDesc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S,
-                           static_cast<const RowsDesc*>(scores_desc));
+                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S,
+                           static_cast<const vlsa_rows_desc*>(scores_desc));
     else
         hipLaunchKernelGGL(k_vlfan_partial_dma_batch<false>, dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
-                           static_cast<const BagDesc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S | (xm << 8),
-                           static_cast<const RowsDesc*>(nullptr));
+                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S | (xm << 8),
+                           static_cast<const vlsa_rows_desc*>(nullptr));
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 
@@ -907,8 +821,8 @@ extern "C" int vlsa_attn_normalise_batch(const void* bag_desc, int B, int P, int
     if (max_N == 0) return VLSA_OK;
     const unsigned int chunks = (unsigned int)((max_N + 1023) / 1024);
     hipLaunchKernelGGL(k_attn_normalise_batch, dim3(chunks, P, B), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const BagDesc*>(bag_desc), static_cast<const RowsDesc*>(scores_desc),
-                       static_cast<const RowsDesc*>(attn_desc), m2, l, (int)kPStride);
+                       static_cast<const vlsa_bag_desc*>(bag_desc), static_cast<const vlsa_rows_desc*>(scores_desc),
+                       static_cast<const vlsa_rows_desc*>(attn_desc), m2, l, (int)kPStride);
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 

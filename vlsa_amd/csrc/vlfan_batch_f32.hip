@@ -12,28 +12,13 @@
 //   * row norms on the VALU from the score fragments (32 FMAs + 2 cross-quad adds per tile).
 // Matrix-pipe load per 16-row tile per wave: 32 f32 steps (scores, 32 cycles each) + 24 bf16 steps (sum, 16 cycles) = 1408
 // cycles; with the sum in f32 as well (round 1) it was 2048 = ~95 % of the pipe at HBM rate, and the kernel sat at 62-64 %.
-#include "vlsa_common.h"
+#define VLSA_STREAM_NT "nt"
+#include "vlfan_stream.h"
 #ifndef VLSA_F32_ABL
 #define VLSA_F32_ABL 0     // timing-only ablations / schedule variants (tools/f32_ablate.py); 0 = the product
 #endif
 
 namespace vlsa {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef f32x4 __attribute__((may_alias)) f32x4_ma;
-typedef float __attribute__((may_alias)) float_ma;
-typedef int __attribute__((may_alias)) int_ma;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-struct BagDesc {
-    const void* X;
-    int64_t N;
-    int64_t ldx;
-};
-struct RowsDesc {  // one [P, ld] fp32 matrix per bag (mirrors vlsa_rows_desc in vlsa_hip.h)
-    float* ptr;
-    int64_t ld;
-};
 
 namespace bf {
 constexpr int kTile = 16;                        // rows per tile
@@ -50,28 +35,16 @@ constexpr int kLdsBytes = kMlOff + 8 * 32 * 4;
 constexpr float kThr = 16.0f;
 }  // namespace bf
 
-// element (row, col) of a wave's fp32 slice image (16 rows x 128 columns) lives at
-// row * 512 + (((col >> 2) ^ row) << 4) + (col & 3) * 4: the 16-B chunk index is XORed with the 4-bit row, so that both the
-// score reads (16 rows x one chunk per quarter wave) and the weighted-sum reads (4 rows x 16 words) hit 64 distinct banks
-__device__ __forceinline__ int fswz(int row, int col) { return row * 512 + ((((col >> 2) ^ (row & 15))) << 4) + ((col & 3) << 2); }
-
-#define VLSA_FBAR()                                          \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-    } while (0)
-
 // S = number of workgroup groups: bag t is streamed by the Gb = G / S workgroups of group t % S only, so S bags are in
 // flight at once, every workgroup sees S times more rows per bag (fewer bag epilogues, better tile quantisation) and a
 // bag leaves Gb instead of G partials behind.
 // kScores: see k_vlfan_partial_dma_batch (vlfan_batch.hip) -- optional per-bag store of the normalised log2-domain scores.
 template <bool kScores>
-__global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDesc* __restrict__ bags, int B,
+__global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const vlsa_bag_desc* __restrict__ bags, int B,
                                                                      const float* __restrict__ qeff, const float* __restrict__ qmeta, int P,
                                                                      float* __restrict__ pm, float* __restrict__ pl,
                                                                      float* __restrict__ pacc, int S,
-                                                                     const RowsDesc* __restrict__ sdesc, const BagDesc one) {
+                                                                     const vlsa_rows_desc* __restrict__ sdesc, const vlsa_bag_desc one) {
     using namespace bf;
     constexpr int D = 512;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -84,42 +57,25 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
 
     unsigned char* ring = smem + w * kWaveRing;
     unsigned char* exch = smem + kRingBytes + rg * kExchGroup;
-    int_ma* tab = reinterpret_cast<int_ma*>(smem + kTabOff);
+    const StreamTab<kTabInts> tab{reinterpret_cast<int_ma*>(smem + kTabOff)};
 
     // ---- bag table: the workgroup's own bags grp, grp + S, ... only (local index lb <-> bag grp + lb * S, <= kMaxLocal entries
     // whatever B is, see k_vlfan_partial_dma_batch); thread lb describes this workgroup's rows of its lb-th bag
     const int nloc = grp < B ? (B - grp + S - 1) / S : 0;
     if (tid < nloc) {
         const int bag_id = grp + tid * S;
-        const BagDesc d = bags ? bags[bag_id] : one;   // bags == null: ONE bag, described in the kernel arguments (single-slide calls)
-        // 32-row units (= one lock-step iteration of the two row groups); the workgroup that gets the remainder
-        // unit rotates with the bag index so that the extra iterations even out over the batch
-        const unsigned long long units = (unsigned long long)((d.N + 31) >> 5);
-        const unsigned int uq = (unsigned int)(units / (unsigned int)G), ur = (unsigned int)(units % (unsigned int)G);
+        const vlsa_bag_desc d = bags ? bags[bag_id] : one;   // bags == null: ONE bag, described in the kernel arguments (single-slide calls)
+        // 32-row units (= one lock-step iteration of the two row groups)
         const unsigned int vb = (unsigned int)((b + tid * 37) % G);  // virtual workgroup index for this bag
-        constexpr bool mine = true;
-        const unsigned long long ubeg = (unsigned long long)vb * uq + (vb < ur ? vb : ur);
-        const long long rbeg = (long long)(ubeg << 5);
-        long long rend = (long long)((ubeg + uq + (vb < ur ? 1u : 0u)) << 5);
-        if (rend > d.N) rend = d.N;
-        const int nrows = (mine && rend > rbeg) ? (int)(rend - rbeg) : 0;
-        const unsigned long long addr = reinterpret_cast<unsigned long long>(d.X) + (unsigned long long)rbeg * d.ldx * 4ull;
-        int_ma* e = tab + tid * kTabInts;
+        int_ma* e = tab.entry(tid);
+        const long long rbeg = stream_split<5, 4, kTile>(d, G, vb, true, e);
         if constexpr (kScores) {
-            const RowsDesc sd = sdesc[bag_id];
+            const vlsa_rows_desc sd = sdesc[bag_id];
             const unsigned long long sp = sd.ptr ? reinterpret_cast<unsigned long long>(sd.ptr + rbeg) : 0ull;
-            e[8] = (int)(unsigned int)sp;
-            e[9] = (int)(sp >> 32);
-            e[10] = (int)sd.ld;
+            e[kEntScoreLo] = (int)(unsigned int)sp;
+            e[kEntScoreHi] = (int)(sp >> 32);
+            e[kEntScorePitch] = (int)sd.ld;
         }
-        e[0] = (int)(unsigned int)addr;
-        e[1] = (int)((addr >> 32) & 0xffffu);
-        e[2] = nrows > 0 ? (int)(((long long)(nrows - 1) * d.ldx + D) * 4) : 0;  // descriptor span in bytes
-        e[3] = (int)(d.ldx * 4);                                                    // row pitch in bytes
-        e[4] = nrows;
-        e[5] = (nrows + kTile - 1) / kTile;
-        e[6] = (int)vb;  // partial slot of this workgroup for this bag
-        e[7] = mine ? 1 : 0;
     }
     // query B-fragments, fp32, scale * log2(e) applied here: lane holds e_p[p = i16][128 cw + 4 kk + g], kk = 0..31
     float qf[32];
@@ -134,66 +90,21 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    auto tab_get = [&](int bag, int k) -> int { return __builtin_amdgcn_readfirstlane(tab[bag * kTabInts + k]); };
-
-    const unsigned int ring_lds = (unsigned int)(uintptr_t)(lds_void_ptr)ring;
-    const int lr = lane >> 5, lc = lane & 31;
-    // LDS-DMA of one 32-row tile of `bag` into ring slot `slot` (see k_vlfan_partial_dma for the layout)
-    // descriptor of the bag the DMA currently streams from, cached in SGPRs (reloaded from the table on a bag change)
-    int ib = -1, ildb = 0;
-    int voff[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // row of piece i within the tile is 2 i + lr
-    i32x4 rsrc = {0, 0, 0, 0x00020000};
-    auto issue_tile = [&](int bag, int tile, int slot) {
-        if (bag != ib) {
-            const int4 e = *reinterpret_cast<const int4*>(smem + kTabOff + bag * (kTabInts * 4));
-            rsrc[0] = __builtin_amdgcn_readfirstlane(e.x);
-            rsrc[1] = __builtin_amdgcn_readfirstlane(e.y);
-            rsrc[2] = __builtin_amdgcn_readfirstlane(e.z);
-            ildb = __builtin_amdgcn_readfirstlane(e.w);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) voff[q] = lr * ildb + cw * 512 + ((lc ^ (2 * q + lr)) << 4);
-            ib = bag;
-        }
-        const int ldb = ildb;
-        const int sbase = tile * kTile * ldb;
-        const unsigned int dst = ring_lds + slot * kSlot;
-        unsigned int keep;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %1\n\t"
-                "s_nop 0\n\t"
-                "buffer_load_dwordx4 %2, %3, %4 offen nt lds\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "s"(dst + i * 1024), "v"(voff[i]), "s"(rsrc), "s"(sbase + i * 2 * ldb)
-                : "memory");
-        }
-    };
-    // this row group's next own tile after (bag, tile): same bag if it has one, else the first of a later bag
-    auto next_of = [&](int bag, int tile, int ntiles_bag, int& nb, int& nt) {
-        if (tile + 2 < ntiles_bag) {
-            nb = bag;
-            nt = tile + 2;
-            return;
-        }
-        nb = bag + 1;
-        while (nb < nloc && tab_get(nb, 5) <= rg) ++nb;
-        nt = rg;
-    };
+    DmaRingF32 dma(ring, lane, cw);  // LDS-DMA of one 16-row tile into a ring slot (vlfan_stream.h)
 
     int kown = 0;      // own tiles consumed so far by this wave; own tile k lives in ring slot k & 1
     int k0 = 0, k1 = 0;  // tiles consumed so far by row group 0 / 1 (for the epilogue's free-slot bookkeeping)
     {
-        int fb = 0;  // first own tile of the whole batch
-        while (fb < nloc && tab_get(fb, 5) <= rg) ++fb;
-        if (fb < nloc) issue_tile(fb, rg, 0);
+        const int fb = stream_first_bag(tab, 0, nloc, rg);  // first own tile of the whole batch
+        if (fb < nloc) {
+            dma.bind(tab.entry(fb), fb);
+            dma.issue(rg, 0);
+        }
     }
 
     
     for (int bag = 0; bag < nloc; ++bag) {   // `bag` = local index; the batch's bag index is grp + bag * S
-        const int nrows = tab_get(bag, 4), ntiles = tab_get(bag, 5);
+        const int nrows = tab.get(bag, kEntRows), ntiles = tab.get(bag, kEntTiles);
         const int niter = (ntiles + 1) >> 1;
         f32x4 acc[8];
 #pragma unroll
@@ -201,9 +112,9 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
         float M = -INFINITY, lsum = 0.f;
         float* srow = nullptr;   // kScores: this lane's query row of the bag's score matrix, at this workgroup's first row
         if constexpr (kScores) {
-            const unsigned long long sp = (unsigned long long)(unsigned int)tab_get(bag, 8) |
-                                          ((unsigned long long)(unsigned int)tab_get(bag, 9) << 32);
-            if (sp != 0 && cw == 0 && i16 < P) srow = reinterpret_cast<float*>(sp) + (size_t)i16 * tab_get(bag, 10) + 4 * g;
+            const unsigned long long sp = (unsigned long long)(unsigned int)tab.get(bag, kEntScoreLo) |
+                                          ((unsigned long long)(unsigned int)tab.get(bag, kEntScoreHi) << 32);
+            if (sp != 0 && cw == 0 && i16 < P) srow = reinterpret_cast<float*>(sp) + (size_t)i16 * tab.get(bag, kEntScorePitch) + 4 * g;
         }
 
         for (int it = 0; it < niter; ++it) {
@@ -216,10 +127,11 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
             float ss = 0.f;
             if (have) {
                 int nb, nt;
-                next_of(bag, tile, ntiles, nb, nt);
+                stream_next<2>(tab, bag, tile, ntiles, nloc, rg, nb, nt);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of slot^1's old contents have returned
                 if (nb < nloc) {
-                    issue_tile(nb, nt, slot ^ 1);
+                    dma.bind(tab.entry(nb), nb);
+                    dma.issue(nt, slot ^ 1);
                     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // this tile landed; the next 8 pieces stay in flight
                 } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -266,13 +178,13 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
                 ss = quad_rows_sum(s0 + s1);  // lanes with the same i16 hold the wave-partial |x_n|^2, n = i16
             }
 
-            VLSA_FBAR();  // readers of the previous exchange are done
+            VLSA_LDS_BARRIER();  // readers of the previous exchange are done
             {
                 unsigned char* mine = exch + cw * kExchWave;
                 *reinterpret_cast<f32x4_ma*>(mine + lane * 16) = S;
                 if (g == 0) reinterpret_cast<float_ma*>(mine + 1024)[i16] = ss;
             }
-            VLSA_FBAR();
+            VLSA_LDS_BARRIER();
             if (have) {
                 f32x4 T, R2;
                 {
@@ -390,7 +302,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
             mlw[w * 32 + i16] = M;
             mlw[w * 32 + 16 + i16] = lsum;
         }
-        VLSA_FBAR();
+        VLSA_LDS_BARRIER();
         {
             const int wo = (rg ^ 1) * 4 + cw;
             // one round of LDS reads: both waves' reference maxima for the 4 queries of my accumulator rows, the
@@ -408,7 +320,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
                 am[r] = (Mm4[r] == -INFINITY) ? 0.f : fast_exp2(Mm4[r] - mn);
                 ao[r] = (Mo4[r] == -INFINITY) ? 0.f : fast_exp2(Mo4[r] - mn);
             }
-            const size_t slotg = (size_t)(grp + bag * S) * G + tab_get(bag, 6);
+            const size_t slotg = (size_t)(grp + bag * S) * G + tab.get(bag, kEntSlot);
             if (w == 0 && g == 0 && i16 < P) {
                 const float Mn = fmaxf(M, Mo);
                 const float fm = (M == -INFINITY) ? 0.f : fast_exp2(M - Mn);
@@ -432,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_f32_batch(const BagDes
                 if (p < P) *reinterpret_cast<f32x4*>(dstp + (size_t)p * D) = v;
             }
         }
-        VLSA_FBAR();  // lent slots and the transpose area are free again
+        VLSA_LDS_BARRIER();  // lent slots and the transpose area are free again
         
     }
 }
@@ -453,12 +365,12 @@ int vlsa_launch_partial_f32_batch(const void* bag_desc, int B, const float* qeff
     }
     if (scores_desc)
         hipLaunchKernelGGL(k_vlfan_partial_f32_batch<true>, dim3(workgroups), dim3(512), bf::kLdsBytes, s,
-                           static_cast<const BagDesc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
-                           static_cast<const RowsDesc*>(scores_desc), BagDesc{nullptr, 0, 0});
+                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
+                           static_cast<const vlsa_rows_desc*>(scores_desc), vlsa_bag_desc{nullptr, 0, 0});
     else
         hipLaunchKernelGGL(k_vlfan_partial_f32_batch<false>, dim3(workgroups), dim3(512), bf::kLdsBytes, s,
-                           static_cast<const BagDesc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
-                           static_cast<const RowsDesc*>(nullptr), BagDesc{nullptr, 0, 0});
+                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
+                           static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{nullptr, 0, 0});
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }
 
@@ -470,7 +382,7 @@ int vlsa_launch_partial_f32_one(const float* X, int64_t N, int64_t ldx, const fl
     static DeviceOnce attr_once;
     if (attr_once.first())
         (void)hipFuncSetAttribute((const void*)k_vlfan_partial_f32_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bf::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_partial_f32_batch<false>, dim3(G), dim3(512), bf::kLdsBytes, s, static_cast<const BagDesc*>(nullptr), 1,
-                       qeff, qmeta, P, pm, pl, pacc, 1, static_cast<const RowsDesc*>(nullptr), BagDesc{X, N, ldx});
+    hipLaunchKernelGGL(k_vlfan_partial_f32_batch<false>, dim3(G), dim3(512), bf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(nullptr), 1,
+                       qeff, qmeta, P, pm, pl, pacc, 1, static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{X, N, ldx});
     return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
 }

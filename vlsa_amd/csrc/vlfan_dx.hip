@@ -26,9 +26,6 @@
 
 namespace vlsa {
 
-typedef f32x4 __attribute__((may_alias)) f32x4_dx;
-typedef float __attribute__((may_alias)) float_dx;
-
 namespace dx {
 constexpr int kD = 512;
 constexpr int kQOff = 0;                  // e_p  [16][512] fp32, swizzled
@@ -36,14 +33,10 @@ constexpr int kDOff = 16 * kD * 4;        // dout [16][512] fp32, swizzled
 constexpr int kLds = 2 * 16 * kD * 4;     // 64 KiB
 }  // namespace dx
 
-struct DxBag {
-    const void* X;
-    long long N, ldx;
-};
 
 struct DxArgs {
-    const DxBag* bags;          // [B] fp32 rows the aggregation read (the projected bags)
-    const DxBag* dxs;           // [B] fp32 gradient rows to write
+    const vlsa_bag_desc* bags;          // [B] fp32 rows the aggregation read (the projected bags)
+    const vlsa_bag_desc* dxs;           // [B] fp32 gradient rows to write
     const int* tile_start;      // [B + 1] first 64-row super tile of every bag
     const float* qeff;          // [16][512] effective unit queries e_p (rows >= P zero)
     const float* dout;          // [B][P][512] upstream gradient of the aggregated rows
@@ -71,14 +64,14 @@ __global__ __launch_bounds__(256) void k_vlfan_dx(const DxArgs a) {
     // e_p -> LDS once
     for (int i = tid; i < 16 * 128; i += 256) {
         const int p = i >> 7, ch = i & 127;
-        *reinterpret_cast<f32x4_dx*>(smem + kQOff + dx_chunk(p, ch)) = *reinterpret_cast<const f32x4*>(a.qeff + p * kD + 4 * ch);
+        *reinterpret_cast<f32x4_ma*>(smem + kQOff + dx_chunk(p, ch)) = *reinterpret_cast<const f32x4*>(a.qeff + p * kD + 4 * ch);
     }
 
     struct Tile { const float* x; float* dxo; long long ldx, lddx; int nrows, bag; };
     auto find = [&](int s) -> Tile {
         const int ts = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
         const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= s)) - 1;
-        const DxBag bag = a.bags[b], o = a.dxs[b];
+        const vlsa_bag_desc bag = a.bags[b], o = a.dxs[b];
         const long long row0 = (long long)(s - a.tile_start[b]) * 64 + 16 * w;
         Tile t;
         t.bag = b;
@@ -117,8 +110,8 @@ __global__ __launch_bounds__(256) void k_vlfan_dx(const DxArgs a) {
         float ss = 0.f;
 #pragma unroll
         for (int ct = 0; ct < 32; ++ct) {
-            const f32x4 q4 = *reinterpret_cast<const f32x4_dx*>(smem + kQOff + dx_chunk(i16, 4 * ct + g));
-            const f32x4 d4 = *reinterpret_cast<const f32x4_dx*>(smem + kDOff + dx_chunk(i16, 4 * ct + g));
+            const f32x4 q4 = *reinterpret_cast<const f32x4_ma*>(smem + kQOff + dx_chunk(i16, 4 * ct + g));
+            const f32x4 d4 = *reinterpret_cast<const f32x4_ma*>(smem + kDOff + dx_chunk(i16, 4 * ct + g));
             const f32x4 x4 = x[ct];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -155,8 +148,8 @@ __global__ __launch_bounds__(256) void k_vlfan_dx(const DxArgs a) {
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int off = dx_chunk(p, 4 * (c2 + k) + (i16 >> 2)) + (i16 & 3) * 4;
-                    const float dv = *reinterpret_cast<const float_dx*>(smem + kDOff + off);
-                    const float ev = *reinterpret_cast<const float_dx*>(smem + kQOff + off);
+                    const float dv = *reinterpret_cast<const float_ma*>(smem + kDOff + off);
+                    const float ev = *reinterpret_cast<const float_ma*>(smem + kQOff + off);
                     accA[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv, Aw[r], accA[k], 0, 0, 0);
                     accU[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(ev, Uw[r], accU[k], 0, 0, 0);
                 }
@@ -187,7 +180,7 @@ __global__ __launch_bounds__(256) void k_vlfan_dx(const DxArgs a) {
                     const int p = i >> 7, ch = i & 127;
                     f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (p < a.P) v = *reinterpret_cast<const f32x4*>(dsrc + p * kD + 4 * ch);
-                    *reinterpret_cast<f32x4_dx*>(smem + kDOff + dx_chunk(p, ch)) = v;
+                    *reinterpret_cast<f32x4_ma*>(smem + kDOff + dx_chunk(p, ch)) = v;
                 }
                 __syncthreads();
                 bag_in_lds = cur.bag;
@@ -246,8 +239,8 @@ extern "C" int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc,
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_dx_delta, dim3(B), dim3(1024), 0, st, dout, out, P, delta_ws);
     DxArgs a{};
-    a.bags = static_cast<const DxBag*>(bag_desc);
-    a.dxs = static_cast<const DxBag*>(dx_desc);
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    a.dxs = static_cast<const vlsa_bag_desc*>(dx_desc);
     a.tile_start = tile_start;
     const QPrepLayout L(D);
     a.qeff = reinterpret_cast<const float*>(static_cast<const unsigned char*>(qprep) + L.qeff);

@@ -16,8 +16,6 @@ constexpr int mfma_lds_bytes() {
     return 4 * kSliceBytes * (F32 ? 2 : 1) + 2 * kExchParity;
 }
 
-__device__ __forceinline__ int swz(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
-
 __device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b, float c) {
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), c, false);
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), c, false);
@@ -25,14 +23,6 @@ __device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b, float c) {
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), c, false);
     return c;
 }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// LDS images are written as raw 16-B words and read back as bf16 fragments: every such access goes through
-// may_alias types so type-based alias analysis can never reorder a fragment read above the staging write.
-typedef u32x4 __attribute__((may_alias)) u32x4_ma;
-typedef bf16x8 __attribute__((may_alias)) bf16x8_ma;
-typedef bf16x4 __attribute__((may_alias)) bf16x4_ma;
-typedef f32x4 __attribute__((may_alias)) f32x4_ma;
 
 // Staging registers for one 32-row tile of this wave's 128-column slice.
 //   bf16: 8 x 16 B per lane; load i covers rows 4i..4i+3, lane -> (row 4i + g, 16-B chunk i16)

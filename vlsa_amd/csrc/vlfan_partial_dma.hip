@@ -13,15 +13,10 @@
 //   * row norms come from the diagonal of X X^T on the matrix pipe (no VALU dot products, no cross-lane
 //     reduction); 1/|x| is v_rsq_f32; the coattn scale * log2(e) is folded into the prepared queries.
 //   * counted s_waitcnt vmcnt(N) + raw s_barrier keep the next tile's DMA in flight across the exchange.
-#include "vlsa_common.h"
+#define VLSA_STREAM_NT ""      // no cache qualifier on the single-bag kernel's DMA loads
+#include "vlfan_stream.h"
 
 namespace vlsa {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef bf16x8 __attribute__((may_alias)) bf16x8_ma;
-typedef f32x4 __attribute__((may_alias)) f32x4_ma;
-typedef float __attribute__((may_alias)) float_ma;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef VLSA_TIMING
 __device__ long long vlsa_dbg_cycles[32];
@@ -43,15 +38,6 @@ constexpr int kExchGroup = 4 * kExchWave;
 constexpr int kLdsBytes = kRingBytes + 2 * kExchGroup;  // 148,480 B
 constexpr float kThr = 16.0f;                   // rescale threshold, log2 units
 }  // namespace dma
-
-__device__ __forceinline__ int swz_off(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
-
-#define VLSA_LDS_BARRIER()                                   \
-    do {                                                     \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-        __builtin_amdgcn_s_barrier();                        \
-        asm volatile("" ::: "memory");                       \
-    } while (0)
 
 template <bool WANT_SCORES>
 __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __restrict__ X, int64_t N, int64_t ldx,
@@ -85,40 +71,10 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __re
     // buffer descriptor over exactly this workgroup's rows: anything past `rend` reads as zero
     const __bf16* xbase = X + rbeg * ldx;
     const unsigned int span = nrows > 0 ? (unsigned int)(((int64_t)(nrows - 1) * ldx + D) * 2) : 0u;
-    // raw buffer descriptor, built by hand and pinned to SGPRs: {base_lo, base_hi (stride 0), num_records, flags}
     const uint64_t xaddr = reinterpret_cast<uint64_t>(xbase);
-    i32x4 rsrc;
-    rsrc[0] = __builtin_amdgcn_readfirstlane((int)(unsigned int)xaddr);
-    rsrc[1] = __builtin_amdgcn_readfirstlane((int)((xaddr >> 32) & 0xffffu));
-    rsrc[2] = __builtin_amdgcn_readfirstlane((int)span);
-    rsrc[3] = 0x00020000;
-    const int ldb = (int)(ldx * 2);  // row pitch in bytes
-    // LDS-DMA lands lane l at slot byte 16 l of the 1-KiB piece (rows 4i + (l >> 4)); to realise the swizzled
-    // image the lane fetches source chunk (l & 15) ^ ((row & 7) << 1); row & 7 = (l >> 4) + 4 (i & 1).
-    const int lr = lane >> 4;
-    const int voff_e = lr * ldb + cw * 256 + (((lane & 15) ^ (lr << 1)) << 4);
-    const int voff_o = lr * ldb + cw * 256 + (((lane & 15) ^ (lr << 1) ^ 8) << 4);
-
-    // The DMA is issued from inline asm on purpose: hipcc would otherwise order every later ds_read of the ring
-    // behind ALL outstanding LDS-DMA (s_waitcnt vmcnt(0)), which serialises the prefetch; we count it ourselves.
-    const unsigned int ring_lds = (unsigned int)(uintptr_t)(lds_void_ptr)ring;  // LDS byte address of this wave's ring
-    auto issue_tile = [&](int tile, int slot) {
-        const int sbase = tile * kTile * ldb;
-        const unsigned int dst = ring_lds + slot * kSlot;
-        unsigned int keep;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            asm volatile(
-                "s_mov_b32 %0, m0\n\t"
-                "s_mov_b32 m0, %1\n\t"
-                "s_nop 0\n\t"
-                "buffer_load_dwordx4 %2, %3, %4 offen lds\n\t"
-                "s_mov_b32 m0, %0"
-                : "=&s"(keep)
-                : "s"(dst + i * 1024), "v"((i & 1) ? voff_o : voff_e), "s"(rsrc), "s"(sbase + i * 4 * ldb)
-                : "memory");
-        }
-    };
+    DmaRingBf16 dma(ring, lane, cw);  // LDS-DMA of one 32-row tile into a ring slot (vlfan_stream.h); descriptor pinned to SGPRs
+    dma.bind(__builtin_amdgcn_readfirstlane((int)(unsigned int)xaddr), __builtin_amdgcn_readfirstlane((int)((xaddr >> 32) & 0xffffu)),
+             __builtin_amdgcn_readfirstlane((int)span), (int)(ldx * 2));
 
     VLSA_STAMP(1);
     // Round 6 -- the start of the kernel in the order that keeps HBM busy (profiles/r05_dma_stamps.txt: half of the kernel was ramp):
@@ -141,12 +97,12 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __re
 #undef VLSA_QLOAD
     }
     const bool first = rg < ntiles, second = rg + 2 < ntiles;      // wave-uniform
-    if (first) issue_tile(rg, 0);
+    if (first) dma.issue(rg, 0);
     // every wave's FIRST tile is queued before anybody's second (the CU serves its waves' requests in issue order, and the first
     // exchange needs all four column quarters of tile 0: without this barrier wave 3's tile 0 sat behind three second tiles --
     // profiles/r06_dma_stamps.txt, first attempt: fragments +6.3 k, wave 0's tile +7.3 k, but the first exchange still at +16 k)
     __builtin_amdgcn_s_barrier();
-    if (second) issue_tile(rg + 2, 1);
+    if (second) dma.issue(rg + 2, 1);
 
     f32x4 acc[8];
 #pragma unroll
@@ -185,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __re
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
-                    xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + swz_off(16 * h + i16, kk * 64 + g * 16));
+                    xa[h][kk] = *reinterpret_cast<const bf16x8_ma*>(xs + swz(16 * h + i16, kk * 64 + g * 16));
             __builtin_amdgcn_sched_barrier(0);  // keep the 8 fragment reads batched ahead of the MFMA chain
             f32x4 Sa[2], Sb[2];
 #pragma unroll
@@ -307,8 +263,8 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __re
             for (int ct = 0; ct < 8; ++ct) {
                 const int c_off = ct * 32 + (i16 & 3) * 8;
                 const int rr = 4 * g + (i16 >> 2);
-                const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz_off(rr, c_off)));
-                const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz_off(16 + rr, c_off)));
+                const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(rr, c_off)));
+                const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(xs + swz(16 + rr, c_off)));
                 const bf16x8 bh = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                 acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, bh, acc[ct], 0, 0, 0);
                 acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bh, acc[ct], 0, 0, 0);
@@ -317,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void k_vlfan_partial_dma(const __bf16* __re
         // the slot just consumed takes the tile after next: every ds_read of it has returned (they fed the MFMAs above)
         if (tile + 4 < ntiles) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            issue_tile(tile + 4, slot);
+            dma.issue(tile + 4, slot);
         }
     }
 

@@ -27,7 +27,22 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
+typedef __attribute__((address_space(3))) void* lds_void_ptr;
+// LDS images are written as raw words (or by LDS-DMA) and read back as typed fragments: every such access goes through
+// may_alias types so type-based alias analysis can never reorder a fragment read above the staging write.
+typedef u32x4 __attribute__((may_alias)) u32x4_ma;
+typedef bf16x8 __attribute__((may_alias)) bf16x8_ma;
+typedef bf16x4 __attribute__((may_alias)) bf16x4_ma;
+typedef f32x4 __attribute__((may_alias)) f32x4_ma;
+typedef float __attribute__((may_alias)) float_ma;
+typedef int __attribute__((may_alias)) int_ma;
+
+// The kernels read the public descriptors (vlsa_hip.h) straight from device memory.
+static_assert(sizeof(vlsa_bag_desc) == 24, "vlsa_bag_desc is part of the ABI");
+static_assert(sizeof(vlsa_rows_desc) == 16, "vlsa_rows_desc is part of the ABI");
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kNormEps = 1e-12f;  // F.normalize eps (model/deepmil.py:187,189)
@@ -55,6 +70,9 @@ __device__ __forceinline__ float quad_rows_max(float v) {
     return v;
 }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// Byte offset of (row, byte_off) in a wave's bf16 slice image (256-byte rows): the 32-byte chunk index is XORed with row & 7.
+__device__ __forceinline__ int swz(int row, int byte_off) { return row * 256 + (byte_off ^ ((row & 7) << 5)); }
 
 // Counter-based dropout mask of the fused attention-score kernels (forward and backward recompute the same bits):
 // keep(seed, row, unit) = mix32(seed ^ row * 0x9E3779B1 ^ unit * 0x85EBCA6B) >= thr, thr = p * 2^32 (murmur3 finaliser).

@@ -918,26 +918,22 @@ class _VlfanBatchAggregateFn(torch.autograd.Function):
         lib, s = nat.load(), _stream()
         B, dev = table.B, out.device
         dout = _f32c(dout)
-        if (table.dt == nat.DT_BF16 and P <= 12) or table.dt == nat.DT_F32:   # the persistent batch kernels (bf16: P <= 12; fp32: any P)
-            G = lib.vlsa_bwd_batch_partials()
-            pm = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-            pl = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-            pacc = torch.empty(G, P, D, dtype=torch.float32, device=dev)
-            prep = torch.empty(lib.vlsa_bwd_batch_prep_bytes(B, D), dtype=torch.uint8, device=dev)
+        persistent = table.dt == nat.DT_F32 or P <= 12   # the persistent batch kernels (bf16: P <= 12; fp32: any P)
+        # partial sums: one per workgroup of the persistent kernel, else G row blocks per bag; reduced together either way
+        G = lib.vlsa_bwd_batch_partials() if persistent else B * max(num_partials(x.shape[0]) for x in table.bags)
+        pm = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        pl = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
+        pacc = torch.empty(G, P, D, dtype=torch.float32, device=dev)
+        prep = torch.empty(lib.vlsa_bwd_batch_prep_bytes(B, D), dtype=torch.uint8, device=dev)
+        if persistent:
             nat.check(lib.vlsa_vlfan_backward_batch(_p(table.desc), B, table.dt, D, _p(qbuf), P, scale, _p(dout), _p(out),
                                                     _p(m2), _p(l), _p(prep), _p(pm), _p(pl), _p(pacc),
                                                     choose_groups([x.shape[0] for x in table.bags], 0), s),
                       "vlsa_vlfan_backward_batch")
-            _, _, dE = vlfan_merge(pm, pl, pacc, normalise=False)
-        else:  # fp32 bags or P > 12: the per-bag kernel over the bag table in ONE launch, partial sums of all bags reduced together
-            G = max(num_partials(x.shape[0]) for x in table.bags)
-            pm = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-            pl = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-            pacc = torch.empty(B * G, P, D, dtype=torch.float32, device=dev)
-            prep = torch.empty(lib.vlsa_bwd_batch_prep_bytes(B, D), dtype=torch.uint8, device=dev)
+        else:  # bf16 bags with P > 12: the per-bag kernel over the bag table in ONE launch
             nat.check(lib.vlsa_vlfan_backward_bags(_p(table.desc), B, table.dt, D, _p(qbuf), P, scale, _p(dout), _p(out), _p(m2),
-                                                   _p(l), _p(prep), _p(pm), _p(pl), _p(pacc), G, s), "vlsa_vlfan_backward_bags")
-            _, _, dE = vlfan_merge(pm, pl, pacc, normalise=False)
+                                                   _p(l), _p(prep), _p(pm), _p(pl), _p(pacc), G // B, s), "vlsa_vlfan_backward_bags")
+        _, _, dE = vlfan_merge(pm, pl, pacc, normalise=False)
         # chain rule to the raw queries (normalisation + gate row) in one launch (round 6; was five torch kernels on [P, 512])
         dQ = torch.empty(nq, D, dtype=torch.float32, device=dev)
         nat.check(lib.vlsa_query_chain(_p(dE.contiguous()), _p(qbuf), nq, int(gated), D, _p(dQ), s), "vlsa_query_chain")
