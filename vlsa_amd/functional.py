@@ -11,36 +11,15 @@ import os
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _native as nat
 from ._native import VlsaNativeError
+from .bag_tables import (ChunkTables, _bag2d, _dt, _need_gpu, _p, _stage_table, _stream, bag_rows, checked_bags,  # noqa: F401
+                         merge_strides)
 
 COATTN_SCALE = 100.0  # exp(coattn_logit_scale), model/deepmil.py:120-126
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_cur_device = getattr(torch._C, "_cuda_getDevice", None)
-
-
-def _stream():
-    """The current HIP stream of the current device as a C pointer.  The raw accessors (what torch.cuda.current_stream() wraps) save
-    ~7 us of Python object construction per call -- this runs several times per bag in the bag-by-bag loops."""
-    if _raw_stream is not None and _cur_device is not None:
-        return ctypes.c_void_p(_raw_stream(_cur_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _need_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise VlsaNativeError(
-                "vlsa_amd runs on MI355X only: got a CPU tensor (there is no CPU fallback; the CPU oracle under "
-                "oracle/ is test infrastructure)")
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -48,31 +27,6 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
-
-
-_BAG_DTYPES = (torch.bfloat16, torch.float32)
-
-
-def _bag2d(X: torch.Tensor) -> torch.Tensor:
-    """[1,N,D] or [N,D] -> [N,D] view with unit inner stride and 16-byte aligned rows (copy only if needed)."""
-    # the common case first (a list of 64 slide-sized bags pays this per bag, and the launch itself is ~0.6 us per bag): a contiguous
-    # [N, D] bf16 / fp32 tensor whose rows are a multiple of 16 bytes, at a 16-byte aligned address
-    if (X.dim() == 2 and X.dtype in _BAG_DTYPES and X.is_contiguous() and (X.shape[1] * X.element_size()) % 16 == 0
-            and X.data_ptr() % 16 == 0):
-        return X
-    if X.dim() == 3:
-        if X.shape[0] != 1:
-            raise AssertionError("X.shape[0] must be 1 (one bag per call; model/deepmil.py:175)")
-        X = X[0]
-    if X.dim() != 2:
-        raise ValueError(f"expected a [N, D] or [1, N, D] bag, got {tuple(X.shape)}")
-    if X.dtype not in (torch.float32, torch.bfloat16):
-        X = X.float()
-    esz = X.element_size()
-    if X.shape[0] > 0 and (X.stride(1) != 1 or (X.stride(0) * esz) % 16 != 0 or X.data_ptr() % 16 != 0
-                           or X.stride(0) < X.shape[1]):
-        X = X.contiguous()
-    return X
 
 
 def _no_bag_grad(*bags):
@@ -151,7 +105,7 @@ def vlfan_partial(X: torch.Tensor, qp: PreparedQueries, kernel: int = nat.KERNEL
         pl.zero_()
         pacc.zero_()
         return pm, pl, pacc, scores
-    dt = nat.DT_F32 if X.dtype == torch.float32 else nat.DT_BF16
+    dt = _dt(X)
     nat.check(lib.vlsa_vlfan_partial(_p(X), dt, N, X.stride(0), D, _p(qp.buf), qp.P, kernel,
                                      _p(pm), _p(pl), _p(pacc), _p(scores), _stream()), "vlsa_vlfan_partial")
     return pm, pl, pacc, scores
@@ -492,9 +446,10 @@ class _SlideTrainFn(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[0]:      # the bag is the output of a trainable Feat_Projecter (fp32 [N, 512]): dL/dX of the aggregation
             dX = torch.empty(N, D, dtype=torch.float32, device=dev)
-            tkeep, p_desc, p_dx, _, p_ts, n_tiles, _ = _row_tables([X2], 64, extra=[dX])
+            tables = ChunkTables.of_list([X2], 64, "vlsa_vlfan_backward_dx", extra=[dX])
+            ts, n_tiles = tables.p_tile_start(64)
             delta = torch.empty(1, nat.P_STRIDE, dtype=torch.float32, device=dev)
-            nat.check(lib.vlsa_vlfan_backward_dx(p_desc, p_dx, 1, D, qprep, P, plan.scale, p_ts, n_tiles, gat("drows"), at("out"), at("m2"),
+            nat.check(lib.vlsa_vlfan_backward_dx(tables.p_desc, tables.p_desc2, 1, D, qprep, P, plan.scale, ts, n_tiles, gat("drows"), at("out"), at("m2"),
                                                  at("l"), _p(delta), s), "vlsa_vlfan_backward_dx")
         return dX, gb[:plan.flat_floats], None
 
@@ -578,7 +533,7 @@ class VlfanInferencePlan:
                     continue
                 k[name] = _p(t)
         nq = self.P + 1 if self.gated else self.P
-        dt = nat.DT_F32 if X.dtype == torch.float32 else nat.DT_BF16
+        dt = _dt(X)
         # one Python -> C crossing for the five launches (this path is host-bound: the handler calls it bag by bag)
         nat.check(lib.vlsa_vlfan_forward_bag(_p(X), dt, N_, X.stride(0), self.D, None if reuse else _p(Q), nq, int(self.gated), self.scale, _p(T),
                                              self.K, _p(logit_scale), -1 if query_pool_module is not None else self.pool, _p(pool_w),
@@ -639,7 +594,7 @@ class VlfanInferencePlan:
 
     def run_partial_only(self, X: torch.Tensor):
         """Just the streaming kernel (for roofline timing); queries must have been prepared by a run()."""
-        dt = nat.DT_F32 if X.dtype == torch.float32 else nat.DT_BF16
+        dt = _dt(X)
         nat.check(self.lib.vlsa_vlfan_partial(_p(X), dt, self.N if self.N is not None else X.shape[0], X.stride(0), self.D, _p(self.qprep), self.P,
                                               self.kernel, _p(self.pm), _p(self.pl), _p(self.pacc),
                                               _p(self.scores), _stream()), "vlfan_partial")
@@ -660,9 +615,10 @@ def _vlfan_dx(bags, qbuf, P: int, scale: float, dout: torch.Tensor, out: torch.T
     # one packed buffer, views handed out: the projecter's backward (_FeatProjectBagsFn) then receives rows that are already contiguous
     dxs = list(torch.empty(sum(x.shape[0] for x in bags), 512, dtype=torch.float32, device=dev).split([x.shape[0] for x in bags]))
     B = len(bags)
-    keep, p_desc, p_dx, _, p_ts, n_tiles, _ = _row_tables(bags, 64, extra=dxs)
+    tables = ChunkTables.of_list(bags, 64, "vlsa_vlfan_backward_dx", extra=dxs)
+    ts, n_tiles = tables.p_tile_start(64)
     delta = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
-    nat.check(lib.vlsa_vlfan_backward_dx(p_desc, p_dx, B, 512, _p(qbuf), P, float(scale), p_ts, n_tiles, _p(_f32c(dout)), _p(out), _p(m2),
+    nat.check(lib.vlsa_vlfan_backward_dx(tables.p_desc, tables.p_desc2, B, 512, _p(qbuf), P, float(scale), ts, n_tiles, _p(_f32c(dout)), _p(out), _p(m2),
                                          _p(l), _p(delta), _stream()), "vlsa_vlfan_backward_dx")
     return dxs
 
@@ -694,7 +650,7 @@ class _VlfanAggregateFn(torch.autograd.Function):
         pl = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
         pacc = torch.empty(G, P, D, dtype=torch.float32, device=dev)
         prep = torch.empty(lib.vlsa_bwd_prep_bytes(D), dtype=torch.uint8, device=dev)
-        dt = nat.DT_F32 if X2.dtype == torch.float32 else nat.DT_BF16
+        dt = _dt(X2)
         if N == 0:
             dE = torch.zeros(P, D, dtype=torch.float32, device=dev)
         else:
@@ -751,7 +707,6 @@ class AttnBuffers:
     ``vlsa_attn_normalise_batch`` turns them into the attention weights in place; ``views[i]`` is bag i's A [P, N_i]."""
 
     def __init__(self, sizes, P: int, device):
-        import numpy as np
         self.sizes, self.P = [int(n) for n in sizes], int(P)
         B = len(self.sizes)
         n = np.asarray(self.sizes, dtype=np.int64)
@@ -766,7 +721,7 @@ class AttnBuffers:
         host[0:2 * B:2] = np.where(n > 0, base + 4 * offs[:B], 0)
         host[1:2 * B:2] = lds
         host[2 * B + 1::3] = n
-        dev = torch.from_numpy(host).to(device)
+        dev = _stage_table(host, device, "AttnBuffers")
         self.desc, self.ndesc = dev[:2 * B].view(B, 2), dev[2 * B:].view(B, 3)
         self._offs, self._lds = offs, lds
         self._views = None
@@ -782,14 +737,6 @@ class AttnBuffers:
         return self._views
 
 
-def _stage_table(host_np, device) -> torch.Tensor:
-    """int64 table -> device through a ring of pinned staging buffers (async; a pageable ``.to(device)`` blocks the host for ~60 us
-    per call -- four such copies were 0.25 ms of a 2.1 ms optimizer step)"""
-    import threading
-    ring = _TABLE_RING.setdefault(threading.get_ident(), _PinnedRing())
-    return ring.stage(host_np.reshape(-1), device).view(host_np.shape)
-
-
 class BagSet(list):
     """A fixed collection of bags -- a split's slides resident in HBM -- checked ONCE: a ``list`` of ``[N_i, 512]`` device tensors (so every
     API that takes a list of bags takes it) that also carries the bags' descriptor rows (pointer, N_i, row stride).  ``forward_bags`` and
@@ -799,25 +746,15 @@ class BagSet(list):
     ``DeviceBagArena``, or tensors nobody frees): the rows hold their addresses."""
 
     def __init__(self, bags=(), D: int = 512, _rows=None):
-        import numpy as np
         if _rows is not None:                   # internal: a sub-set of a checked set
             super().__init__(bags)
             self.rows, self.D = _rows, D
         else:
-            keep = []
-            for i, x in enumerate(bags):
-                _need_gpu(x)
-                x = _bag2d(x)
-                if x.shape[1] != D or x.shape[0] < 1 or (i > 0 and (x.dtype != keep[0].dtype or x.device != keep[0].device)):
-                    raise VlsaNativeError("a BagSet holds non-empty bags with D == 512, one dtype (bf16 or fp32) and one device")
-                if torch.is_grad_enabled() and x.requires_grad:
-                    raise VlsaNativeError("a BagSet holds bags without a gradient of their own (data, not activations)")
-                keep.append(x)
-            super().__init__(keep)
-            self.rows = np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in keep], dtype=np.int64).reshape(len(keep), 3)
-            self.D = D
+            super().__init__(checked_bags(bags, D, "a BagSet holds non-empty bags with D == 512, one dtype (bf16 or fp32) and one device",
+                                          non_empty=True, no_grad="a BagSet holds bags without a gradient of their own (data, not activations)"))
+            self.rows, self.D = bag_rows(self), D
         self.sizes = tuple(int(n) for n in self.rows[:, 1])
-        self.dt = (nat.DT_F32 if self[0].dtype == torch.float32 else nat.DT_BF16) if len(self) else nat.DT_BF16
+        self.dt = _dt(self[0]) if len(self) else nat.DT_BF16
         self._chunks, self._groups, self._desc = {}, {}, None
 
     def take(self, indices) -> "BagSet":
@@ -842,8 +779,11 @@ class BagSet(list):
     def desc(self) -> torch.Tensor:
         """the [B, 3] int64 descriptor table on the bags' device (uploaded once per set)"""
         if self._desc is None:
-            self._desc = _stage_table(self.rows, self[0].device)
+            self._desc = _stage_table(self.rows, self[0].device, "a BagSet's descriptor table (not yet uploaded)")
         return self._desc
+
+
+_BATCH_BAGS = "the batched path takes bags with D == 512, one dtype (bf16 or fp32) and one device per batch"
 
 
 class _BagTable:
@@ -854,24 +794,19 @@ class _BagTable:
         B = len(bags)
         if not (1 <= B <= lib.vlsa_batch_max_bags()):
             raise ValueError(f"batch size {B} outside [1, {lib.vlsa_batch_max_bags()}]")
-        import numpy as np
         if isinstance(bags, BagSet) and bags.D == D:      # checked once, rows kept: no per-bag work
             self.bags, self.B, self.D, self.dt, self.desc = bags, B, D, bags.dt, bags.desc()
             self.sizes = bags.sizes
             return
-        keep, rows = [], []
-        for i, x in enumerate(bags):
-            _need_gpu(x)
-            x = _bag2d(x)
-            if x.shape[1] != D or (i > 0 and x.dtype != keep[0].dtype):
-                raise VlsaNativeError("the batched path takes bags with D == 512 and one dtype (bf16 or fp32) per batch")
-            keep.append(x)
-            n = x.shape[0]
-            rows.append((x.data_ptr(), n, x.stride(0) if n > 0 else D))
-        self.bags, self.B, self.D = keep, B, D
-        self.dt = nat.DT_F32 if keep[0].dtype == torch.float32 else nat.DT_BF16
-        self.desc = _stage_table(np.asarray(rows, dtype=np.int64).reshape(B, 3), keep[0].device)
-        self.sizes = tuple(r[1] for r in rows)
+        self.bags, self.B, self.D = checked_bags(bags, D, _BATCH_BAGS), B, D
+        rows = bag_rows(self.bags, D)
+        self.dt = _dt(self.bags[0])
+        self.desc = _stage_table(rows, self.bags[0].device, "the batched path over a plain list of bags")
+        self.sizes = tuple(rows[:, 1].tolist())
+
+    def groups(self, reserved_cus: int = 0) -> int:
+        """bags the persistent kernels keep in flight (kept by a ``BagSet``)"""
+        return self.bags.groups(reserved_cus) if isinstance(self.bags, BagSet) else choose_groups(self.sizes, reserved_cus)
 
 
 class _VlfanBatchAggregateFn(torch.autograd.Function):
@@ -887,7 +822,7 @@ class _VlfanBatchAggregateFn(torch.autograd.Function):
         qp = prepare_queries(Q, gated, coattn_scale)
         P = qp.P
         ws = torch.empty(lib.vlsa_batch_workspace_bytes(B, P, D), dtype=torch.uint8, device=dev)
-        groups = table.bags.groups(0) if isinstance(table.bags, BagSet) else choose_groups(table.sizes, 0)
+        groups = table.groups(0)
         nat.check(lib.vlsa_vlfan_partial_batch_scores(_p(table.desc), B, table.dt, D, _p(qp.buf), P, _p(ws), 0, groups,
                                                       None if attn is None else _p(attn.desc), s),
                   "vlsa_vlfan_partial_batch")
@@ -897,9 +832,7 @@ class _VlfanBatchAggregateFn(torch.autograd.Function):
         m2 = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
         l = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
         out = torch.empty(B, P, D, dtype=torch.float32, device=dev)
-        st = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, P * D, G * nat.P_STRIDE, G * nat.P_STRIDE, G * P * D,
-                                  nat.P_STRIDE, nat.P_STRIDE, P * D)
-        nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, P, D, 1, st, _p(m2), _p(l), _p(out), s),
+        nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, P, D, 1, merge_strides(G, P, D), _p(m2), _p(l), _p(out), s),
                   "vlsa_vlfan_merge_batch_strided")
         if attn is not None:   # scores -> attention weights in place, with the bag-global (m2, l)
             nat.check(lib.vlsa_attn_normalise_batch(_p(table.desc), B, P, attn.max_n, _p(attn.desc), _p(m2), _p(l), _p(attn.desc), s),
@@ -920,7 +853,7 @@ class _VlfanBatchAggregateFn(torch.autograd.Function):
         dout = _f32c(dout)
         persistent = table.dt == nat.DT_F32 or P <= 12   # the persistent batch kernels (bf16: P <= 12; fp32: any P)
         # partial sums: one per workgroup of the persistent kernel, else G row blocks per bag; reduced together either way
-        G = lib.vlsa_bwd_batch_partials() if persistent else B * max(num_partials(x.shape[0]) for x in table.bags)
+        G = lib.vlsa_bwd_batch_partials() if persistent else B * max(num_partials(n) for n in table.sizes)
         pm = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
         pl = torch.empty(G, nat.P_STRIDE, dtype=torch.float32, device=dev)
         pacc = torch.empty(G, P, D, dtype=torch.float32, device=dev)
@@ -928,7 +861,7 @@ class _VlfanBatchAggregateFn(torch.autograd.Function):
         if persistent:
             nat.check(lib.vlsa_vlfan_backward_batch(_p(table.desc), B, table.dt, D, _p(qbuf), P, scale, _p(dout), _p(out),
                                                     _p(m2), _p(l), _p(prep), _p(pm), _p(pl), _p(pacc),
-                                                    choose_groups([x.shape[0] for x in table.bags], 0), s),
+                                                    table.groups(0), s),
                       "vlsa_vlfan_backward_batch")
         else:  # bf16 bags with P > 12: the per-bag kernel over the bag table in ONE launch
             nat.check(lib.vlsa_vlfan_backward_bags(_p(table.desc), B, table.dt, D, _p(qbuf), P, scale, _p(dout), _p(out), _p(m2),
@@ -959,12 +892,12 @@ def vlfan_cross_attention_bags(bags, Q: torch.Tensor, gated: bool = False, coatt
     if torch.is_grad_enabled():
         _no_bag_grad(*[x for x in bags if not (x.dtype == torch.float32 and x.shape[-1] == 512)])   # dX: fp32 D == 512 bags only
     table = _BagTable(bags)
-    if any(x.shape[0] == 0 for x in table.bags):
+    if 0 in table.sizes:
         raise VlsaNativeError("empty bag in a batch")
     if not want_attn:
         return _VlfanBatchAggregateFn.apply(Q.float(), bool(gated), float(coattn_scale), table, None, *bags)
     P = Q.shape[0] - (1 if gated else 0)
-    attn = AttnBuffers([x.shape[0] for x in table.bags], P, table.desc.device)
+    attn = AttnBuffers(table.sizes, P, table.desc.device)
     out = _VlfanBatchAggregateFn.apply(Q.float(), bool(gated), float(coattn_scale), table, attn, *bags)
     return out, attn.views
 
@@ -972,10 +905,6 @@ def vlfan_cross_attention_bags(bags, Q: torch.Tensor, gated: bool = False, coatt
 # ------------------------------------------------------------------------------------------------------
 # FeatMIL / DeepMIL / zero-shot pieces (model/deepmil.py:16-67,222-292; model/layers.py:85-153)
 # ------------------------------------------------------------------------------------------------------
-def _dt(X):
-    return nat.DT_F32 if X.dtype == torch.float32 else nat.DT_BF16
-
-
 def _scored_pool_raw(X2: torch.Tensor, scores: Optional[torch.Tensor]):
     lib = nat.load()
     N, D = X2.shape
@@ -1076,36 +1005,63 @@ def attn_scores(H: torch.Tensor, Hg: Optional[torch.Tensor], b1, bg, w2, b2) -> 
     return a
 
 
-_SCORE_TILING = {}
-
-
-def _score_tiling(f32: bool, gated: bool):
-    """(rows of the score kernel's largest tile, row tiles per round of the CUs) -- vlsa_gated_scores_tiling, asked once."""
-    key = (f32, gated)
-    t = _SCORE_TILING.get(key)
-    if t is None:
-        mr, rt = ctypes.c_int(0), ctypes.c_int(0)
-        nat.check(nat.load().vlsa_gated_scores_tiling(nat.DT_F32 if f32 else nat.DT_BF16, int(gated), ctypes.addressof(mr),
-                                                     ctypes.addressof(rt)), "vlsa_gated_scores_tiling")
-        t = _SCORE_TILING[key] = (mr.value, rt.value)
-    return t
-
-
-_SCORE_BIG_TILE = {}
+_SCORE_TILES = {}
 _NO_FUSED_POOL = os.environ.get("VLSA_GS_NO_FUSED_POOL", "") == "1"      # (A/B hook: scores and pooling as two launches)
 
 
-def _score_big_tile(f32: bool, gated: bool):
-    """(tile height of the persistent LDS-DMA score kernel, rows in a batch from which to use it) -- vlsa_gated_scores_big_tile;
-    (0, 0): not for this dtype / module."""
-    key = (f32, gated)
-    t = _SCORE_BIG_TILE.get(key)
+def _score_tiles(name: str, f32: bool, gated: bool, second=ctypes.c_int):
+    """the two numbers the library's ``name`` answers per (bag dtype, module), asked once"""
+    t = _SCORE_TILES.get((name, f32, gated))
     if t is None:
-        rows, mn = ctypes.c_int(0), ctypes.c_int64(0)
-        nat.check(nat.load().vlsa_gated_scores_big_tile(nat.DT_F32 if f32 else nat.DT_BF16, int(gated), ctypes.addressof(rows),
-                                                       ctypes.addressof(mn)), "vlsa_gated_scores_big_tile")
-        t = _SCORE_BIG_TILE[key] = (rows.value, mn.value)
+        a, b = ctypes.c_int(0), second(0)
+        nat.check(getattr(nat.load(), name)(nat.DT_F32 if f32 else nat.DT_BF16, int(gated), ctypes.addressof(a), ctypes.addressof(b)), name)
+        t = _SCORE_TILES[(name, f32, gated)] = (a.value, b.value)
     return t
+
+
+def _score_tiling(f32: bool, gated: bool):
+    """(rows of the score kernel's largest tile, row tiles per round of the CUs)"""
+    return _score_tiles("vlsa_gated_scores_tiling", f32, gated)
+
+
+def _score_big_tile(f32: bool, gated: bool):
+    """(tile height of the persistent LDS-DMA score kernel, rows in a batch from which to use it); (0, 0): not for this dtype / module."""
+    return _score_tiles("vlsa_gated_scores_big_tile", f32, gated, ctypes.c_int64)
+
+
+def score_tile_rows(sizes, f32: bool, gated: bool, allow_big: bool, tiling=None):
+    """(rows per tile of the batched score launch over bags of these sizes, whether that is the persistent LDS-DMA kernel).
+    allow_big: False keeps the LDS-DMA kernel out (``pool_bags`` under VLSA_GS_NO_FUSED_POOL=1).  tiling: (max_rows, round_tiles,
+    big_rows, big_min) where the library is not to be asked (tests without one)."""
+    max_rows, round_tiles, big_rows, big_min = tiling or (*_score_tiling(f32, gated), *_score_big_tile(f32, gated))
+    tiles = lambda r: sum((n + r - 1) // r for n in sizes)   # noqa: E731
+    if allow_big and big_rows and sum(sizes) >= big_min:     # a workgroup per row tile of up to big_rows rows
+        rpt = big_rows
+        if tiles(rpt) < 256:                                 # less than one round: the lowest tiles that still fit it
+            rpt = max_rows + 32
+            while rpt < big_rows and tiles(rpt) > 256:
+                rpt += 32
+        return rpt, True
+    rpt = max_rows
+    if tiles(max_rows) < round_tiles:                        # less than one round of the 256 CUs: smaller tiles
+        rpt = 16
+        while rpt < max_rows and tiles(rpt) > round_tiles:
+            rpt += 16
+    return rpt, False
+
+
+def pool_rows(desc: torch.Tensor, B: int, dt: int, a: Optional[torch.Tensor], a_off: Optional[torch.Tensor]):
+    """(pooled [B, 512], m2 [B, 16], l [B, 16]) of B <= 64 bags behind a descriptor table: softmax_b(a) X_b per bag (a None: the row
+    means) as G pooling partials per bag (vlsa_scored_pool_partial_batch) and their merge -- two launches"""
+    lib, s, dev = nat.load(), _stream(), desc.device
+    G = max(1, min(64, 512 // B))
+    f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)  # noqa: E731
+    pm, pl, pacc, m2, l, pooled = f(B * G, nat.P_STRIDE), f(B * G, nat.P_STRIDE), f(B * G, 512), f(B, nat.P_STRIDE), f(B, nat.P_STRIDE), f(B, 512)
+    nat.check(lib.vlsa_scored_pool_partial_batch(_p(desc), B, dt, 512, _p(a), _p(a_off), G, _p(pm), _p(pl), _p(pacc), s),
+              "vlsa_scored_pool_partial_batch")
+    nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, 1, 512, 1, merge_strides(G, 1, 512), _p(m2), _p(l), _p(pooled), s),
+              "vlsa_vlfan_merge_batch_strided")
+    return pooled, m2, l
 
 
 _POOL_WS: dict = {}        # N -> vlsa_gated_scores_pool_ws_floats(N)
@@ -1158,75 +1114,26 @@ class FusedAttnScores:
         raw scores of all bags (vlsa_gated_scores_batch), softmax-weighted row sums (vlsa_scored_pool_partial_batch), fold.
         Returns (pooled [B, 512] fp32, scores [sum N_i] fp32, offsets [B + 1]) -- model/layers.py:103-122,137-153 per bag."""
         lib, s, dev = nat.load(), _stream(), bags[0].device
-        gated, B = Wg is not None, len(bags)
-        if not (1 <= B <= 64):
-            raise ValueError("1..64 bags per call")
+        gated, B = Wg is not None, _chunk_len(bags)
         prep = self._packed(dev, Wa, ba, Wg, bg, w2, c)
-        rows = [x.shape[0] for x in bags]
-        f32 = bags[0].dtype == torch.float32
-        max_rows, round_tiles = _score_tiling(f32, bool(gated))
-        rpt = max_rows
-        big_rows, big_min = _score_big_tile(f32, bool(gated))
-        fused = bool(big_rows) and sum(rows) >= big_min and not _NO_FUSED_POOL
-        if big_rows and not fused and not gated:
-            big_rows = 0                          # (the ungated module's plain score launches keep the fragment-order kernel)
-        if fused:            # a large batch: the persistent LDS-DMA kernel, scores and pooling in ONE launch (a workgroup per row tile)
-            rpt = big_rows
-            if sum((n + rpt - 1) // rpt for n in rows) < 256:                    # less than one round: the lowest tiles that still fit it
-                rpt = max_rows + 32
-                while rpt < big_rows and sum((n + rpt - 1) // rpt for n in rows) > 256:
-                    rpt += 32
-        elif sum((n + max_rows - 1) // max_rows for n in rows) < round_tiles:    # less than one round of the 256 CUs: smaller tiles
-            rpt = 16
-            while rpt < max_rows and sum((n + rpt - 1) // rpt for n in rows) > round_tiles:
-                rpt += 16
-        import numpy as np
-        stage = getattr(self, "_stage", None)
-        if stage is None or stage[0] != B:
-            meta = torch.empty(4 * B + (B + 2) // 2, dtype=torch.int64).pin_memory()
-            stage = self._stage = [B, meta, None]
-        elif stage[2] is not None:
-            stage[2].synchronize()                 # the previous call's async table upload has read the staging buffer
-        meta = stage[1]
-        m = meta.numpy()
-        m[:3 * B] = np.asarray([(x.data_ptr(), n, x.stride(0)) for x, n in zip(bags, rows)], dtype=np.int64).reshape(-1)
-        offs = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(rows, out=offs[1:])
-        m[3 * B:4 * B] = offs[:B]
-        ts = m[4 * B:].view(np.int32)
-        ts[0] = 0
-        np.cumsum([(n + rpt - 1) // rpt for n in rows], out=ts[1:B + 1])
-        n_tiles, total = int(ts[B]), int(offs[B])
-        meta_d = meta.to(dev, non_blocking=True)
-        stage[2] = torch.cuda.Event()
-        stage[2].record()
-        base = meta_d.data_ptr()
-        a = torch.empty(total, dtype=torch.float32, device=dev)
-        dt = nat.DT_F32 if f32 else nat.DT_BF16
-        if fused:
+        dt = _dt(bags[0])
+        rows = bag_rows(bags)
+        rpt, fused = score_tile_rows(rows[:, 1].tolist(), dt == nat.DT_F32, gated, not _NO_FUSED_POOL)
+        t = ChunkTables.from_host(rows, dt, rpt, dev, "FusedAttnScores.pool_bags")
+        ts, n_tiles = t.p_tile_start(rpt)
+        a = torch.empty(t.total, dtype=torch.float32, device=dev)
+        if fused:            # a large batch: the persistent LDS-DMA kernel, scores and pooling in ONE launch
             ws = torch.empty(n_tiles * 514, dtype=torch.float32, device=dev)
             pooled = torch.empty(B, 512, dtype=torch.float32, device=dev)
-            nat.check(lib.vlsa_gated_scores_pool_batch(base, B, dt, 512, _p(prep), int(gated), base + 32 * B, n_tiles, rpt, _p(a),
-                                                       base + 24 * B, _p(ws), _p(pooled), s), "vlsa_gated_scores_pool_batch")
-            self._keep = (meta_d, bags, ws)            # the kernels read these
-            return pooled, a, offs
-        G = max(1, min(64, 512 // B))
-        pm = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pl = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pacc = torch.empty(B * G, 512, dtype=torch.float32, device=dev)
-        m2 = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        l = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pooled = torch.empty(B, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_gated_scores_batch(base, B, dt, 512, _p(prep), int(gated), base + 32 * B, n_tiles, rpt, _p(a),
-                                              base + 24 * B, total, s), "vlsa_gated_scores_batch")
-        nat.check(lib.vlsa_scored_pool_partial_batch(base, B, dt, 512, _p(a), base + 24 * B, G, _p(pm), _p(pl), _p(pacc), s),
-                  "vlsa_scored_pool_partial_batch")
-        st = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, 512, G * nat.P_STRIDE, G * nat.P_STRIDE, G * 512,
-                                  nat.P_STRIDE, nat.P_STRIDE, 512)
-        nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, 1, 512, 1, st, _p(m2), _p(l), _p(pooled), s),
-                  "vlsa_vlfan_merge_batch_strided")
-        self._keep = (meta_d, bags)                # the kernels read these
-        return pooled, a, offs
+            nat.check(lib.vlsa_gated_scores_pool_batch(t.p_desc, B, dt, 512, _p(prep), int(gated), ts, n_tiles, rpt, _p(a),
+                                                       t.p_row_off, _p(ws), _p(pooled), s), "vlsa_gated_scores_pool_batch")
+            self._keep = (t, bags, ws)                 # the kernels read these
+            return pooled, a, t.offs
+        nat.check(lib.vlsa_gated_scores_batch(t.p_desc, B, dt, 512, _p(prep), int(gated), ts, n_tiles, rpt, _p(a),
+                                              t.p_row_off, t.total, s), "vlsa_gated_scores_batch")
+        pooled, _, _ = pool_rows(t.desc, B, dt, a, t.row_off)
+        self._keep = (t, bags)                         # the kernels read these
+        return pooled, a, t.offs
 
     def scores_and_pool(self, X2, Wa, ba, Wg, bg, w2, c, adapter=None):
         """(pooled [1, 512] fp32, raw scores [N]) of ONE bag from ONE host call (vlsa_gated_scores_pool): bf16 bags -- scores and pooling
@@ -1287,81 +1194,6 @@ class FusedAttnScores:
         return a
 
 
-class _PinnedRing:
-    """Small ring of pinned int64 staging buffers for the descriptor tables of the multi-bag kernels: the upload is an ASYNC copy
-    on the current stream (a pageable `.to(device)` blocks the host for tens of microseconds per call); a slot is reused only after
-    the copy that read it has completed (event)."""
-
-    def __init__(self, slots: int = 8, words: int = 1024):
-        self.slots, self.words, self.bufs, self.events, self.i = slots, words, None, None, 0
-
-    def stage(self, host_np, device):
-        import numpy as np
-        n = int(host_np.shape[0])
-        if n > self.words or not torch.cuda.is_available():
-            return torch.from_numpy(np.ascontiguousarray(host_np)).to(device)
-        if self.bufs is None:
-            self.bufs = [torch.empty(self.words, dtype=torch.int64).pin_memory() for _ in range(self.slots)]
-            self.events = [None] * self.slots
-        k = self.i % self.slots
-        self.i += 1
-        if self.events[k] is not None:
-            self.events[k].synchronize()
-        self.bufs[k].numpy()[:n] = host_np
-        dev = self.bufs[k][:n].to(device, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(device))
-        self.events[k] = ev
-        return dev
-
-
-_TABLE_RING = {}     # per host thread (autograd runs backward functions on its own thread)
-
-
-def _row_tables(bags, tile_rows: int, extra=None):
-    """ONE upload for the tables the multi-bag backward kernels take: vlsa_bag_desc [B, 3] (pointer, N, row stride), optionally a
-    second table (``extra``: e.g. the gradient rows), row offsets [B] (int64) and tile_start [B + 1] (int32, tiles of
-    ``tile_rows`` rows).  Returns (device buffer, ptr of desc, ptr of extra desc or None, ptr of row_off, ptr of tile_start,
-    n_tiles, row offsets as a list)."""
-    import threading
-    B = len(bags)
-    if B == 1 and bags[0].shape[0] > 0:
-        # one bag (the bag-by-bag training loop): the tables are written on the device from by-value arguments -- one launch
-        # instead of numpy bookkeeping + a pinned staging copy + an event per call
-        x, lib = bags[0], nat.load()
-        s = _stream()
-        buf = torch.empty(8, dtype=torch.int64, device=x.device)      # 64 bytes per call: no state shared between calls
-        ex = extra[0] if extra is not None else None
-        n_tiles = lib.vlsa_fill_one_bag_tables(_p(buf), _p(x), x.shape[0], x.stride(0), _p(ex), 0 if ex is None else ex.stride(0), int(tile_rows), s)
-        if n_tiles < 0:
-            nat.check(n_tiles, "vlsa_fill_one_bag_tables")
-        base = buf.data_ptr()
-        o = 6 if ex is not None else 3
-        return buf, base, (base + 24 if ex is not None else None), base + 8 * o, base + 8 * (o + 1), int(n_tiles), [0, int(x.shape[0])]
-    import numpy as np
-    rows = [int(x.shape[0]) for x in bags]
-    n64 = 3 * B + (3 * B if extra is not None else 0) + B + (B + 2) // 2
-    host = np.zeros(n64, dtype=np.int64)
-    host[:3 * B] = np.asarray([(x.data_ptr(), n, x.stride(0)) for x, n in zip(bags, rows)], dtype=np.int64).reshape(-1)
-    o = 3 * B
-    if extra is not None:
-        host[o:o + 3 * B] = np.asarray([(x.data_ptr(), n, x.stride(0)) for x, n in zip(extra, rows)], dtype=np.int64).reshape(-1)
-        o += 3 * B
-    offs = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(rows, out=offs[1:])
-    host[o:o + B] = offs[:B]
-    ts = host[o + B:].view(np.int32)
-    ts[0] = 0
-    np.cumsum([(n + tile_rows - 1) // tile_rows for n in rows], out=ts[1:B + 1])
-    n_tiles = int(ts[B])
-    ring = _TABLE_RING.setdefault(threading.get_ident(), _PinnedRing())
-    dev = ring.stage(host, bags[0].device)
-    base = dev.data_ptr()
-    p_extra = base + 24 * B if extra is not None else None
-    p_off = base + 8 * o
-    return dev, base, p_extra, p_off, p_off + 8 * B, n_tiles, offs
-
-
 class _AttnScoresFn(torch.autograd.Function):
     """Raw (gated) attention scores a [N] of one bag with a gradient for the pooling module's parameters: forward = the fused MFMA
     kernel (vlsa_gated_scores), backward = vlsa_attn_scores_backward (hidden activations recomputed tile by tile, dW = dH^T X in
@@ -1384,11 +1216,12 @@ class _AttnScoresFn(torch.autograd.Function):
         dev = X2.device
         da = _f32c(da).reshape(-1)
         tile_rows = int(lib.vlsa_mlp_bwd_tile_rows(_dt(X2)))
-        keep, p_desc, _, p_off, p_ts, n_tiles, _ = _row_tables([X2], tile_rows)
+        t = ChunkTables.of_list([X2], tile_rows, "vlsa_attn_scores_backward")
+        ts, n_tiles = t.p_tile_start(tile_rows)
         ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(1 if gated else 0, n_tiles), dtype=torch.uint8, device=dev)
         dW = torch.empty(2 if gated else 1, 256, 512, dtype=torch.float32, device=dev)
         dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_attn_scores_backward(p_desc, 1, _dt(X2), 512, _p(prep), int(gated), p_ts, n_tiles, _p(da), p_off, _p(ws),
+        nat.check(lib.vlsa_attn_scores_backward(t.p_desc, 1, _dt(X2), 512, _p(prep), int(gated), ts, n_tiles, _p(da), t.p_row_off, _p(ws),
                                                 _p(dW), _p(dvec), ctx.drop[0], ctx.drop[1], _stream()), "vlsa_attn_scores_backward")
         w2_shape, c_shape = ctx.shapes
         return (None, None, dW[0], dvec[0, :256], dW[1] if gated else None, dvec[0, 256:] if gated else None,
@@ -1423,16 +1256,17 @@ class _AttnPoolFn(torch.autograd.Function):
         tile_rows = int(lib.vlsa_mlp_bwd_tile_rows(_dt(X2)))
         need_dx = ctx.needs_input_grad[0]          # the bag itself carries a gradient (a trainable Feat_Projecter in front)
         dX = torch.empty(N, 512, dtype=torch.float32, device=dev) if need_dx else None
-        keep, p_desc, p_dx, p_off, p_ts, n_tiles, _ = _row_tables([X2], tile_rows, extra=[dX] if need_dx else None)
+        t = ChunkTables.of_list([X2], tile_rows, "vlsa_attn_scores_backward", extra=[dX] if need_dx else None)
+        ts, n_tiles = t.p_tile_start(tile_rows)
         ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(1 if gated else 0, n_tiles), dtype=torch.uint8, device=dev)
         dW = torch.empty(2 if gated else 1, 256, 512, dtype=torch.float32, device=dev)
         dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_attn_scores_backward(p_desc, 1, _dt(X2), 512, _p(prep), int(gated), p_ts, n_tiles, _p(da), p_off, _p(ws),
+        nat.check(lib.vlsa_attn_scores_backward(t.p_desc, 1, _dt(X2), 512, _p(prep), int(gated), ts, n_tiles, _p(da), t.p_row_off, _p(ws),
                                                 _p(dW), _p(dvec), ctx.drop[0], ctx.drop[1], s), "vlsa_attn_scores_backward")
         if need_dx:
             aw = torch.exp2(a * 1.4426950408889634 - m2[0]) / l[0]          # [N] softmax weights of the pooling
-            nat.check(lib.vlsa_attn_scores_backward_dx(p_desc, p_dx, 1, _dt(X2), 512, _p(prep), _p(prep_t), int(gated), p_ts, n_tiles, _p(da),
-                                                       _p(aw), _p(dp), p_off, ctx.drop[0], ctx.drop[1], s), "vlsa_attn_scores_backward_dx")
+            nat.check(lib.vlsa_attn_scores_backward_dx(t.p_desc, t.p_desc2, 1, _dt(X2), 512, _p(prep), _p(prep_t), int(gated), ts, n_tiles, _p(da),
+                                                       _p(aw), _p(dp), t.p_row_off, ctx.drop[0], ctx.drop[1], s), "vlsa_attn_scores_backward_dx")
             if X2.dtype != torch.float32:
                 dX = dX.to(X2.dtype)
         w2_shape, c_shape = ctx.shapes
@@ -1461,67 +1295,57 @@ def attn_scores_autograd(X2: torch.Tensor, fused: "FusedAttnScores", Wa, ba, Wg,
     return _AttnScoresFn.apply(X2, fused, Wa, ba, Wg, bg, w2, c, float(drop_p or 0.0), int(seed or 0))
 
 
-class AttnBagsPlan:
+def _chunk_len(bags) -> int:
+    if not (1 <= len(bags) <= 64):
+        raise ValueError("1..64 bags per call")
+    return len(bags)
+
+
+class _ChunkPlan:
+    """What the plans of the batched routes share: the ``ChunkTables`` of a chunk of <= 64 bags under the names the launches read.
+    A ``BagSet`` keeps its plans, so the second call on the same set does no table work."""
+
+    def __init__(self, tables: ChunkTables):
+        self.tables = t = tables
+        self.B, self.sizes, self.dt, self.total, self.offs = t.B, t.sizes, t.dt, t.total, t.offs
+
+    desc = property(lambda self: self.tables.desc)
+    a_off = property(lambda self: self.tables.row_off)
+
+    @classmethod
+    def of(cls, bags, *args):
+        """the plan of a chunk: a ``BagSet`` keeps its plans (built on first use from its descriptor table); a list gets a fresh one"""
+        if not isinstance(bags, BagSet):
+            return cls(bags, *args)
+        plans = bags.__dict__.setdefault("_plans", {})
+        p = plans.get((cls, *args))
+        if p is None:
+            p = plans[(cls, *args)] = cls(bags, *args)
+        return p
+
+
+def _chunk_tables(bags, route: str) -> ChunkTables:
+    """the tables of a chunk derived on the device: from a ``BagSet``'s descriptor (uploaded once per set) or the one of a set's
+    projected bags; a plain list of bags (rows that carry a gradient of their own) has its descriptor staged from the host first
+    -- not possible inside a graph capture"""
+    desc = bags.desc() if isinstance(bags, (BagSet, ProjectedBags)) else None
+    if desc is None:
+        desc = _stage_table(bag_rows(bags), bags[0].device, route)
+    return ChunkTables.from_device(desc, bags.sizes if isinstance(bags, BagSet) else [int(x.shape[0]) for x in bags], _dt(bags[0]))
+
+
+class AttnBagsPlan(_ChunkPlan):
     """Device tables of one chunk of <= 64 bags for the batched DeepMIL training route (vlsa_gated_scores_batch_train,
     vlsa_attn_pool_backward_batch): the descriptor table, score offsets a_off [B] (int64), the score kernel's tile_start (tiles of
     ``rpt`` rows) and the backward's (tiles of vlsa_mlp_bwd_tile_rows).  Derived from the descriptor ON THE DEVICE by in-stream ops
-    -- no staging copy, so a plan may also be built inside a graph capture once the descriptor is up.  A ``BagSet`` keeps its plans."""
+    -- no staging copy, so a plan may also be built inside a graph capture once the descriptor is up."""
 
-    def __init__(self, bags, gated: bool, desc: torch.Tensor):
-        lib = nat.load()
-        self.B = B = len(bags)
-        self.sizes = sizes = [int(x.shape[0]) for x in bags]
-        self.f32 = bags[0].dtype == torch.float32
-        self.dt = nat.DT_F32 if self.f32 else nat.DT_BF16
-        self.total = sum(sizes)
-        self.offs = [0]
-        for n in sizes:
-            self.offs.append(self.offs[-1] + n)
-        max_rows, round_tiles = _score_tiling(self.f32, gated)
-        big_rows, big_min = _score_big_tile(self.f32, gated)
-        tiles = lambda r: sum((n + r - 1) // r for n in sizes)   # noqa: E731
-        rpt = max_rows
-        if big_rows and self.total >= big_min:             # a large bf16 batch: the persistent LDS-DMA score kernel (scores only)
-            rpt = big_rows
-            if tiles(rpt) < 256:
-                rpt = max_rows + 32
-                while rpt < big_rows and tiles(rpt) > 256:
-                    rpt += 32
-        elif tiles(max_rows) < round_tiles:
-            rpt = 16
-            while rpt < max_rows and tiles(rpt) > round_tiles:
-                rpt += 16
-        self.rpt = rpt
-        self.tile_rows = tr = int(lib.vlsa_mlp_bwd_tile_rows(self.dt))
-        self.n_tiles_f, self.n_tiles_b = tiles(rpt), tiles(tr)
-        self.desc = desc
-        n = desc[:, 1]
-        self.a_off = (torch.cumsum(n, 0) - n).contiguous()
-        self.ts_f = torch.zeros(B + 1, dtype=torch.int32, device=desc.device)
-        self.ts_f[1:] = torch.cumsum(torch.div(n + (rpt - 1), rpt, rounding_mode="floor"), 0)
-        self.ts_b = torch.zeros(B + 1, dtype=torch.int32, device=desc.device)
-        self.ts_b[1:] = torch.cumsum(torch.div(n + (tr - 1), tr, rounding_mode="floor"), 0)
-
-    @staticmethod
-    def of(bags, gated: bool) -> "AttnBagsPlan":
-        """the plan of a chunk: kept by a ``BagSet``; a plain list of bags (rows that carry a gradient: the projected bags) gets a
-        fresh one, its descriptor staged from the host -- not possible inside a graph capture"""
-        if isinstance(bags, BagSet):
-            plans = bags.__dict__.setdefault("_attn_plans", {})
-            p = plans.get(bool(gated))
-            if p is None:
-                if bags._desc is None and torch.cuda.is_current_stream_capturing():
-                    raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
-                p = plans[bool(gated)] = AttnBagsPlan(bags, gated, bags.desc())
-            return p
-        desc = bags.desc() if isinstance(bags, ProjectedBags) else None
-        if desc is not None:                    # a BagSet's bags behind a Feat_Projecter: table derived on the device
-            return AttnBagsPlan(bags, gated, desc)
-        if torch.cuda.is_current_stream_capturing():
-            raise VlsaNativeError("the batched DeepMIL route captures over a BagSet (bags without a gradient of their own) only")
-        import numpy as np
-        rows = np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in bags], dtype=np.int64).reshape(len(bags), 3)
-        return AttnBagsPlan(bags, gated, torch.from_numpy(rows).to(bags[0].device))
+    def __init__(self, bags, gated: bool):
+        super().__init__(_chunk_tables(bags, "the batched DeepMIL route over a plain list of bags"))
+        self.rpt, _ = score_tile_rows(self.sizes, self.dt == nat.DT_F32, gated, True)
+        self.tile_rows = int(nat.load().vlsa_mlp_bwd_tile_rows(self.dt))
+        self.ts_f, self.n_tiles_f = self.tables.tile_start(self.rpt)
+        self.ts_b, self.n_tiles_b = self.tables.tile_start(self.tile_rows)
 
 
 class _AttnPoolBagsFn(torch.autograd.Function):
@@ -1540,19 +1364,7 @@ class _AttnPoolBagsFn(torch.autograd.Function):
         nat.check(lib.vlsa_gated_scores_batch_train(_p(plan.desc), B, plan.dt, 512, _p(prep), int(gated), _p(plan.ts_f), plan.n_tiles_f,
                                                     plan.rpt, _p(a), _p(plan.a_off), plan.total, float(drop_p), _p(seed_word), s),
                   "vlsa_gated_scores_batch_train")
-        G = max(1, min(64, 512 // B))
-        pm = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pl = torch.empty(B * G, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pacc = torch.empty(B * G, 512, dtype=torch.float32, device=dev)
-        m2 = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        l = torch.empty(B, nat.P_STRIDE, dtype=torch.float32, device=dev)
-        pooled = torch.empty(B, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_scored_pool_partial_batch(_p(plan.desc), B, plan.dt, 512, _p(a), _p(plan.a_off), G, _p(pm), _p(pl), _p(pacc), s),
-                  "vlsa_scored_pool_partial_batch")
-        st = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, 512, G * nat.P_STRIDE, G * nat.P_STRIDE, G * 512,
-                                  nat.P_STRIDE, nat.P_STRIDE, 512)
-        nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, 1, 512, 1, st, _p(m2), _p(l), _p(pooled), s),
-                  "vlsa_vlfan_merge_batch_strided")
+        pooled, m2, l = pool_rows(plan.desc, B, plan.dt, a, plan.a_off)
         ctx.save_for_backward(a, m2, l, pooled, prep, prep_t, seed_word)
         ctx.plan, ctx.gated, ctx.drop_p = plan, gated, float(drop_p)
         ctx.shapes = (w2.shape, c.shape)
@@ -1581,8 +1393,7 @@ class _AttnPoolBagsFn(torch.autograd.Function):
         dxs = [None] * B
         if need_dx:
             dX = torch.empty(plan.total, 512, dtype=torch.float32, device=dev)
-            n = plan.desc[:, 1]
-            dx_desc = torch.stack([plan.a_off * 2048 + dX.data_ptr(), n, torch.full_like(n, 512)], 1).contiguous()   # (in-stream)
+            dx_desc = plan.tables.packed_desc(dX.data_ptr())
             nat.check(lib.vlsa_attn_scores_backward_dx_seeded(_p(plan.desc), _p(dx_desc), B, plan.dt, 512, _p(prep), _p(prep_t), int(gated),
                                                               _p(plan.ts_b), plan.n_tiles_b, _p(da), _p(aw), _p(dp), _p(plan.a_off),
                                                               ctx.drop_p, _p(seed_word), s), "vlsa_attn_scores_backward_dx_seeded")
@@ -1602,9 +1413,7 @@ def attn_pool_bags_autograd(bags, fused: "FusedAttnScores", Wa, ba, Wg, bg, w2, 
     ONE autograd node (_AttnPoolBagsFn).  drop_p > 0 (gated only): training-mode dropout with the seed read from ``seed_word`` (a
     device int64 word; bag b uses bag_drop_seed(seed, b)).  Inside a graph capture the weights are packed inside the capture, so
     the graph never reads a packed block that a later repack or a dropped cache could free."""
-    B = len(bags)
-    if not (1 <= B <= 64):
-        raise ValueError("1..64 bags per call")
+    B = _chunk_len(bags)
     gated = Wg is not None
     drop_p = float(drop_p or 0.0) if gated else 0.0
     if drop_p and (seed_word is None or not seed_word.is_cuda or seed_word.dtype != torch.int64):
@@ -1625,22 +1434,9 @@ def attn_pool_bags_autograd(bags, fused: "FusedAttnScores", Wa, ba, Wg, bg, w2, 
 def mean_pool_bags(bags) -> torch.Tensor:
     """Row means [B, 512] of up to 64 validated [N_i, 512] device bags (one dtype) in two launches (the 'mean' pooling of
     FeatMIL / DeepMIL over a batch: model/deepmil.py:57-58,271-272 per bag)."""
-    lib, s, dev, B = nat.load(), _stream(), bags[0].device, len(bags)
-    if not (1 <= B <= 64):
-        raise ValueError("1..64 bags per call")
-    import numpy as np
-    desc = torch.from_numpy(np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in bags], dtype=np.int64)).to(dev)
-    G = max(1, min(64, 512 // B))
-    f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)  # noqa: E731
-    pm, pl, pacc, m2, l, out = f(B * G, nat.P_STRIDE), f(B * G, nat.P_STRIDE), f(B * G, 512), f(B, nat.P_STRIDE), f(B, nat.P_STRIDE), f(B, 512)
-    dt = nat.DT_F32 if bags[0].dtype == torch.float32 else nat.DT_BF16
-    nat.check(lib.vlsa_scored_pool_partial_batch(_p(desc), B, dt, 512, None, None, G, _p(pm), _p(pl), _p(pacc), s),
-              "vlsa_scored_pool_partial_batch")
-    st = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, 512, G * nat.P_STRIDE, G * nat.P_STRIDE, G * 512,
-                              nat.P_STRIDE, nat.P_STRIDE, 512)
-    nat.check(lib.vlsa_vlfan_merge_batch_strided(_p(pm), _p(pl), _p(pacc), B, G, 1, 512, 1, st, _p(m2), _p(l), _p(out), s),
-              "vlsa_vlfan_merge_batch_strided")
-    return out
+    B = _chunk_len(bags)
+    desc = _stage_table(bag_rows(bags), bags[0].device, "mean_pool_bags")
+    return pool_rows(desc, B, _dt(bags[0]), None, None)[0]
 
 
 class FusedFeatProjecter:
@@ -1718,64 +1514,35 @@ class _FeatProjectFn(torch.autograd.Function):
         nat.check(lib.vlsa_feat_project_rowstats(_p(dY), dY.stride(0), _p(Y), Y.stride(0), N, _p(prep), _p(stats), s),
                   "vlsa_feat_project_rowstats")
         tile_rows = int(lib.vlsa_mlp_bwd_tile_rows(_dt(X2)))
-        keep, p_desc, p_dy, p_off, p_ts, n_tiles, _ = _row_tables([X2], tile_rows, extra=[dY])
+        t = ChunkTables.of_list([X2], tile_rows, "vlsa_feat_project_backward", extra=[dY])
+        ts, n_tiles = t.p_tile_start(tile_rows)
         ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(2, n_tiles), dtype=torch.uint8, device=dev)
         dW = torch.empty(512, 512, dtype=torch.float32, device=dev)
         dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_feat_project_backward(p_desc, p_dy, 1, _dt(X2), _p(prep), p_ts, n_tiles, _p(stats), p_off, _p(ws), _p(dW),
+        nat.check(lib.vlsa_feat_project_backward(t.p_desc, t.p_desc2, 1, _dt(X2), _p(prep), ts, n_tiles, _p(stats), t.p_row_off, _p(ws), _p(dW),
                                                  _p(dvec), s), "vlsa_feat_project_backward")
         hb, hg, hbt = ctx.has
         return None, None, dW, dvec[0] if hb else None, dvec[1] if hg else None, dvec[2] if hbt else None, None
 
 
-class FeatProjBagsPlan:
+class FeatProjBagsPlan(_ChunkPlan):
     """Tables of one chunk of <= 64 bags for the batched Feat_Projecter (vlsa_feat_project_batch, vlsa_feat_project_rowstats_batch,
     vlsa_feat_project_backward with B bags): the descriptor table, the row offsets of the packed output and tile_start for the forward
-    (tiles of ``rt`` rows, chosen from the chunk's TOTAL row count) -- for a plain list ONE upload (_row_tables); for a ``BagSet``
-    derived from its descriptor on the device by in-stream ops and kept with the set (nothing is staged per call, so the call can
-    also run inside a graph capture), together with the backward's tile_start."""
+    (tiles of ``rt`` rows, chosen from the chunk's TOTAL row count) -- for a plain list ONE upload; for a ``BagSet`` derived from its
+    descriptor on the device by in-stream ops and kept with the set (nothing is staged per call, so the call can also run inside a
+    graph capture), together with the backward's tile_start (tiles of ``tr`` rows)."""
 
     def __init__(self, bags):
         lib = nat.load()
-        is_set = isinstance(bags, BagSet)
-        self.bags, self.B = bags, len(bags)
-        self.sizes = [int(n) for n in (bags.sizes if is_set else [x.shape[0] for x in bags])]
-        self.dt = bags.dt if is_set else _dt(bags[0])
-        self.total = sum(self.sizes)
-        self.offs = [0]
-        for n in self.sizes:
-            self.offs.append(self.offs[-1] + n)
-        self.rt = rt = int(lib.vlsa_feat_project_batch_tile_rows(self.dt, self.total))
-        self.tr = tr = int(lib.vlsa_mlp_bwd_tile_rows(self.dt))
-        self.n_tiles_b = sum((n + tr - 1) // tr for n in self.sizes)
-        self.on_device = is_set
-        if is_set:
-            if bags._desc is None and torch.cuda.is_current_stream_capturing():
-                raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
-            desc = bags.desc()
-            n = desc[:, 1]
-            self.n_rows = n
-            self.row_off = (torch.cumsum(n, 0) - n).contiguous()
-            ts_f = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
-            ts_f[1:] = torch.cumsum(torch.div(n + (rt - 1), rt, rounding_mode="floor"), 0)
-            self.ts_b = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
-            self.ts_b[1:] = torch.cumsum(torch.div(n + (tr - 1), tr, rounding_mode="floor"), 0)
-            self.keep = (desc, ts_f)
-            self.p_desc, self.p_off, self.p_ts = desc.data_ptr(), self.row_off.data_ptr(), ts_f.data_ptr()
-            self.n_tiles = sum((n + rt - 1) // rt for n in self.sizes)
-        else:
-            if self.B > 1 and torch.cuda.is_current_stream_capturing():
-                raise VlsaNativeError("the batched Feat_Projecter captures over a BagSet only (its tables are derived on the device)")
-            self.keep, self.p_desc, _, self.p_off, self.p_ts, self.n_tiles, _ = _row_tables(bags, rt)
-
-    @staticmethod
-    def of(bags) -> "FeatProjBagsPlan":
-        if isinstance(bags, BagSet):
-            p = bags.__dict__.get("_featproj_plan")
-            if p is None:
-                p = bags.__dict__["_featproj_plan"] = FeatProjBagsPlan(bags)
-            return p
-        return FeatProjBagsPlan(bags)
+        self.bags, self.on_device = bags, isinstance(bags, BagSet)
+        dt = bags.dt if self.on_device else _dt(bags[0])
+        self.rt = rt = int(lib.vlsa_feat_project_batch_tile_rows(dt, sum(bags.sizes if self.on_device else [x.shape[0] for x in bags])))
+        self.tr = int(lib.vlsa_mlp_bwd_tile_rows(dt))
+        super().__init__(ChunkTables.from_device(bags.desc(), bags.sizes, dt) if self.on_device
+                         else ChunkTables.of_list(bags, rt, "the batched Feat_Projecter over a plain list of bags"))
+        self.p_ts_f, self.n_tiles_f = self.tables.p_tile_start(rt)
+        if self.on_device:
+            self.tables.tile_start(self.tr)     # the backward's: derived with the plan, not inside a backward pass
 
 
 class ProjectedBags(list):
@@ -1788,11 +1555,10 @@ class ProjectedBags(list):
         self.plan, self._desc = plan, None
 
     def desc(self) -> Optional[torch.Tensor]:
-        p = self.plan
-        if not p.on_device:
+        if not self.plan.on_device:
             return None
         if self._desc is None:
-            self._desc = torch.stack([p.row_off * 2048 + self[0].data_ptr(), p.n_rows, torch.full_like(p.n_rows, 512)], 1).contiguous()
+            self._desc = self.plan.tables.packed_desc(self[0].data_ptr())
         return self._desc
 
 
@@ -1801,8 +1567,8 @@ def _feat_project_bags_launch(plan: FeatProjBagsPlan, prep: torch.Tensor, eps: f
     lib, dev = nat.load(), prep.device
     Y = torch.empty(plan.total, 512, dtype=torch.float32, device=dev)
     stats = torch.empty(plan.total, 4, dtype=torch.float32, device=dev) if train else None
-    nat.check(lib.vlsa_feat_project_batch(plan.p_desc, plan.B, plan.dt, 512, _p(prep), float(eps), plan.p_ts, plan.n_tiles, plan.rt, _p(Y),
-                                          plan.p_off, _p(stats), _stream()), "vlsa_feat_project_batch")
+    nat.check(lib.vlsa_feat_project_batch(plan.tables.p_desc, plan.B, plan.dt, 512, _p(prep), float(eps), plan.p_ts_f, plan.n_tiles_f, plan.rt, _p(Y),
+                                          plan.tables.p_row_off, _p(stats), _stream()), "vlsa_feat_project_batch")
     return Y, stats
 
 
@@ -1838,16 +1604,18 @@ class _FeatProjectBagsFn(torch.autograd.Function):
             if any(g.data_ptr() != base + 2048 * o for g, o in zip(grads, plan.offs)):
                 packed = torch.cat(grads)
                 grads, base = [packed], packed.data_ptr()
-            dy_desc = torch.stack([plan.row_off * 2048 + base, plan.n_rows, torch.full_like(plan.n_rows, 512)], 1).contiguous()
-            p_desc, p_dy, p_off, p_ts, n_tiles = plan.p_desc, dy_desc.data_ptr(), plan.p_off, plan.ts_b.data_ptr(), plan.n_tiles_b
+            t, dy_desc = plan.tables, plan.tables.packed_desc(base)
+            p_dy = dy_desc.data_ptr()
         else:
-            keep, p_desc, p_dy, p_off, p_ts, n_tiles, _ = _row_tables(plan.bags, plan.tr, extra=grads)
-        nat.check(lib.vlsa_feat_project_rowstats_batch(p_dy, B, _p(Y), p_off, plan.total, _p(prep), _p(stats), s),
+            t = ChunkTables.of_list(plan.bags, plan.tr, "the batched Feat_Projecter over a plain list of bags", extra=grads)
+            p_dy = t.p_desc2
+        ts, n_tiles = t.p_tile_start(plan.tr)
+        nat.check(lib.vlsa_feat_project_rowstats_batch(p_dy, B, _p(Y), t.p_row_off, plan.total, _p(prep), _p(stats), s),
                   "vlsa_feat_project_rowstats_batch")
         ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(2, n_tiles), dtype=torch.uint8, device=dev)
         dW = torch.empty(512, 512, dtype=torch.float32, device=dev)
         dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_feat_project_backward(p_desc, p_dy, B, plan.dt, _p(prep), p_ts, n_tiles, _p(stats), p_off, _p(ws), _p(dW),
+        nat.check(lib.vlsa_feat_project_backward(t.p_desc, p_dy, B, plan.dt, _p(prep), ts, n_tiles, _p(stats), t.p_row_off, _p(ws), _p(dW),
                                                  _p(dvec), s), "vlsa_feat_project_backward")
         hb, hg, hbt = ctx.has
         return None, None, dW, dvec[0] if hb else None, dvec[1] if hg else None, dvec[2] if hbt else None, None
@@ -1861,9 +1629,7 @@ def feat_project_bags(bags, fused: "FusedFeatProjecter", W, b, gamma, beta, eps:
     (_FeatProjectBagsFn).  Inside
     a graph capture the weights are packed inside the capture, so a replay never reads a packed block that a later repack or a
     dropped cache could free."""
-    B = len(bags)
-    if not (1 <= B <= 64):
-        raise ValueError("1..64 bags per call")
+    B = _chunk_len(bags)
     _need_gpu(bags[0])
     dev = bags[0].device
     if torch.cuda.is_current_stream_capturing():
@@ -1961,36 +1727,18 @@ class VlfanBatchPlan:
         if len(bags) != self.B:
             raise ValueError(f"expected {self.B} bags, got {len(bags)}")
         if isinstance(bags, BagSet) and bags.D == self.D:      # checked once, descriptor rows kept: one array assignment
-            if self._desc_ev is not None:
-                self._desc_ev.synchronize()
-            self._desc_np[:] = bags.rows
-            self._bags, self.dt = bags, bags.dt
-            self.groups = bags.groups(self.reserved_cus)
-            if self.want_attn and (self.attn is None or tuple(self.attn.sizes) != bags.sizes):
-                self.attn = AttnBuffers(bags.sizes, self.P, self.desc.device)
-            self.desc.copy_(self.desc_host, non_blocking=True)
-            if self.desc_host.is_pinned():
-                self._desc_ev = torch.cuda.Event()
-                self._desc_ev.record()
-            return
-        keep, rows = [], []
-        for i, x in enumerate(bags):
-            if not validated:
-                _need_gpu(x)
-                x = _bag2d(x)
-                if x.shape[1] != self.D or (i > 0 and x.dtype != keep[0].dtype):
-                    raise VlsaNativeError("the batched path takes bags with D == 512 and one dtype (bf16 or fp32) per batch")
-            keep.append(x)
-            n = x.shape[0]
-            rows.append((x.data_ptr(), n, x.stride(0) if n > 0 else self.D))
+            keep, rows, sizes, self.dt, self.groups = bags, bags.rows, bags.sizes, bags.dt, bags.groups(self.reserved_cus)
+        else:
+            keep = list(bags) if validated else checked_bags(bags, self.D, _BATCH_BAGS)
+            rows = bag_rows(keep, self.D)
+            sizes = tuple(rows[:, 1].tolist())
+            self.dt, self.groups = _dt(keep[0]), choose_groups(sizes, self.reserved_cus)  # bags in flight
         if self._desc_ev is not None:
             self._desc_ev.synchronize()            # the previous table's async copy has read the staging buffer
         self._desc_np[:] = rows
         self._bags = keep
-        self.dt = nat.DT_F32 if keep[0].dtype == torch.float32 else nat.DT_BF16
-        self.groups = choose_groups([r[1] for r in rows], self.reserved_cus)  # bags in flight
-        if self.want_attn and (self.attn is None or self.attn.sizes != [r[1] for r in rows]):
-            self.attn = AttnBuffers([r[1] for r in rows], self.P, self.desc.device)
+        if self.want_attn and (self.attn is None or tuple(self.attn.sizes) != sizes):
+            self.attn = AttnBuffers(sizes, self.P, self.desc.device)
         self.desc.copy_(self.desc_host, non_blocking=True)
         if self.desc_host.is_pinned():
             self._desc_ev = torch.cuda.Event()
@@ -2062,7 +1810,7 @@ def zeroshot_pool_bags(bags, T: torch.Tensor, logit_scale: torch.Tensor, k: Opti
     table = _BagTable(bags)
     B, dev = table.B, table.desc.device
     out = torch.empty(B, K, dtype=torch.float32, device=dev)
-    sizes = [x.shape[0] for x in table.bags]
+    sizes = table.sizes
     ls = _f32c(logit_scale).reshape(1)
     for k0 in range(0, K, nat.MAX_P):
         Tk = T[k0:k0 + nat.MAX_P]
@@ -2071,7 +1819,7 @@ def zeroshot_pool_bags(bags, T: torch.Tensor, logit_scale: torch.Tensor, k: Opti
         sc = AttnBuffers(sizes, Pk, dev)
         ws = torch.empty(lib.vlsa_batch_workspace_bytes(B, Pk, table.D), dtype=torch.uint8, device=dev)
         nat.check(lib.vlsa_vlfan_partial_batch_scores(_p(table.desc), B, table.dt, table.D, _p(qp.buf), Pk, _p(ws), 0,
-                                                      choose_groups(sizes, 0), _p(sc.desc), s), "vlsa_vlfan_partial_batch_scores")
+                                                      table.groups(0), _p(sc.desc), s), "vlsa_vlfan_partial_batch_scores")
         part = out if (k0 == 0 and Pk == K) else torch.empty(B, Pk, dtype=torch.float32, device=dev)
         nat.check(lib.vlsa_topk_mean_batch(_p(table.desc), _p(sc.desc), B, Pk, 0 if k is None else int(k), _p(ls), _p(part), s),
                   "vlsa_topk_mean_batch")
@@ -2106,50 +1854,27 @@ def query_pool_attention(rows: torch.Tensor, module) -> Tuple[torch.Tensor, torc
 
 
 # ---- DSMIL (model/deepmil.py:638-721): the dual-stream baseline as two streaming passes over a table of bags ---------------------
-class DsmilBagsPlan:
+class DsmilBagsPlan(_ChunkPlan):
     """Device tables of one chunk of <= 64 bags for vlsa_dsmil_forward_batch / _backward_batch: the descriptor table, part_start
     [B + 1] (bag b owns vlsa_dsmil_parts(N_b) partial records -- a function of N_b alone, so a bag's result is the same in any
     batch) and the attention offsets a_off.  Derived from the descriptor ON THE DEVICE by in-stream ops, so a plan may be built
-    inside a graph capture once the descriptor is up.  A ``BagSet`` keeps its plan."""
+    inside a graph capture once the descriptor is up."""
 
-    def __init__(self, bags, desc: torch.Tensor):
+    def __init__(self, bags):
         lib = nat.load()
-        self.B = len(bags)
-        self.sizes = [int(x.shape[0]) for x in bags]
-        self.dt = nat.DT_F32 if bags[0].dtype == torch.float32 else nat.DT_BF16
-        self.total = sum(self.sizes)
+        super().__init__(_chunk_tables(bags, "the batched DSMIL route over a plain list of bags"))
         self.n_parts = sum(int(lib.vlsa_dsmil_parts(n)) for n in self.sizes)
-        self.desc = desc
-        n = desc[:, 1]
-        self.a_off = (torch.cumsum(n, 0) - n).contiguous()
-        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=desc.device)
+        n = self.desc[:, 1]
+        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
         self.part_start[1:] = torch.cumsum(torch.clamp(torch.div(n + 511, 512, rounding_mode="floor"), 1, 64), 0)   # vlsa_dsmil_parts
-
-    @staticmethod
-    def of(bags) -> "DsmilBagsPlan":
-        if isinstance(bags, BagSet):
-            p = bags.__dict__.get("_dsmil_plan")
-            if p is None:
-                if bags._desc is None and torch.cuda.is_current_stream_capturing():
-                    raise VlsaNativeError("a BagSet's descriptor table must be uploaded (BagSet.desc()) before a graph capture")
-                p = bags.__dict__["_dsmil_plan"] = DsmilBagsPlan(bags, bags.desc())
-            return p
-        desc = bags.desc() if isinstance(bags, ProjectedBags) else None
-        if desc is not None:
-            return DsmilBagsPlan(bags, desc)
-        if torch.cuda.is_current_stream_capturing():
-            raise VlsaNativeError("the batched DSMIL route captures over a BagSet only (its tables are derived on the device)")
-        import numpy as np
-        rows = np.asarray([(x.data_ptr(), x.shape[0], x.stride(0)) for x in bags], dtype=np.int64).reshape(len(bags), 3)
-        return DsmilBagsPlan(bags, torch.from_numpy(rows).to(bags[0].device))
 
 
 def dsmil_state_views(state: torch.Tensor, B: int, C: int) -> dict:
     """the named pieces of a vlsa_dsmil_forward_batch state block (see include/vlsa_hip.h)"""
-    off = (ctypes.c_int64 * 9)()
+    names = ("crit", "cmax", "m2", "l", "xcrit", "qmax", "u", "z", "bm")
+    off = (ctypes.c_int64 * len(names))()
     total = int(nat.load().vlsa_dsmil_state_floats(B, C, off))
     o = list(off) + [total]
-    names = ("crit", "cmax", "m2", "l", "xcrit", "qmax", "u", "z", "bm")
     shapes = ((B, 16), (B, 16), (B, 16), (B, 16), (B, C, 512), (B, C, 256), (B, C, 512), (B, C, 512), (B, C, 256))
     out = {k: state[o[i]:o[i + 1]].view(*sh) for i, (k, sh) in enumerate(zip(names, shapes))}
     out["crit"] = out["crit"].view(torch.int32)
@@ -2202,9 +1927,7 @@ def dsmil_bags(bags, Wc, bc, Wq, bq, Wv, bv, Wf, bf, drop_p: float = 0.0, seed_w
     """DSMIL over a chunk of 1..64 bags ([N_i, 512], one dtype, N_i >= 1, not re-checked: a ``BagSet``, projected bags or validated
     tensors): (logits [B, C], attention [sum N_i] or None, critical rows [B, C] int32), differentiable w.r.t. the eight parameters.  drop_p > 0: training-mode
     dropout on the value side, the seed read from ``seed_word`` (device int64; bag b uses bag_drop_seed(seed, b))."""
-    B = len(bags)
-    if not (1 <= B <= 64):
-        raise ValueError("1..64 bags per call")
+    B = _chunk_len(bags)
     _need_gpu(bags[0], Wc)
     _no_bag_grad(*bags)
     drop_p = float(drop_p or 0.0)

@@ -82,8 +82,7 @@ class ShardedVlfanPlan:
         nq = self.P + 1 if pl_.gated else self.P
         c, p = nat.check, VF._p
         c(lib.vlsa_prepare_queries(p(Q), nq, self.D, int(pl_.gated), pl_.scale, p(pl_.qprep), s), "prepare_queries")
-        dt = nat.DT_F32 if X.dtype == torch.float32 else nat.DT_BF16
-        c(lib.vlsa_vlfan_partial(p(X), dt, pl_.N, X.stride(0), self.D, p(pl_.qprep), self.P, pl_.kernel, p(pl_.pm),
+        c(lib.vlsa_vlfan_partial(p(X), VF._dt(X), pl_.N, X.stride(0), self.D, p(pl_.qprep), self.P, pl_.kernel, p(pl_.pm),
                                  p(pl_.pl), p(pl_.pacc), p(self.scores[slot]), s), "vlfan_partial")
         rec = self.rec[slot]
         # fold the workgroup partials into the compact record in place: m2 -> rec[0:16], l -> rec[16:32], acc -> rec[32:]
@@ -405,8 +404,7 @@ class ShardedVlfanBatchPlan:
     def _set_groups(self, groups):
         P, D, rf = self.P, self.D, self.rf
         self.G = G = int(self.lib.vlsa_batch_partials_per_bag_ex(self.B, self.reserved_cus, groups))
-        self._st_local = (ctypes.c_int64 * 9)(nat.P_STRIDE, nat.P_STRIDE, P * D, G * nat.P_STRIDE, G * nat.P_STRIDE,
-                                              G * P * D, rf, rf, rf)
+        self._st_local = VF.merge_strides(G, P, D, out=(rf, rf, rf))      # the outputs land in the compact records
 
     def set_bags(self, local_shards):
         """local_shards: this rank's rows of every bag, in the caller's bag order"""

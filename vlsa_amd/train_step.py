@@ -103,8 +103,8 @@ class TrainStep:
     # -- graph ------------------------------------------------------------------------------------------------------------------
     @staticmethod
     def _key(bags, t, e):
-        rows = bags.rows.tobytes() if isinstance(bags, VF.BagSet) else tuple((x.data_ptr(), x.shape[0], x.stride(0)) for x in bags)
-        return (rows, t.data_ptr(), None if e is None else e.data_ptr(), t.shape)
+        rows = bags.rows if isinstance(bags, VF.BagSet) else VF.bag_rows(bags)
+        return (rows.tobytes(), t.data_ptr(), None if e is None else e.data_ptr(), t.shape)
 
     def _side(self, bags, t, e):
         """one EAGER step on the capture stream (the step before a capture): whatever the step creates lazily -- allocator pools of
