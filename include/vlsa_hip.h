@@ -471,6 +471,28 @@ int vlsa_topk_values(const float* S, int C, int64_t N, int k, void* workspace, f
 int vlsa_topk_mean_batch(const void* bag_desc, const void* scores_desc, int B, int C, int k, const float* logit_scale, float* out,
                          void* stream);
 
+/* The same launch for the differentiable zero-shot route (prompt pre-training: trainable text features through logit pooling):
+ * out is bit-equal to vlsa_topk_mean_batch's, and for 1 <= k <= 32 idx [B, C, k] (int32) holds the pooled rows of every (bag, class)
+ * as rows within the bag: descending score, ties to the lower row, -1 where N_b < k.  k <= 0: no index is written (idx may be NULL). */
+int vlsa_topk_select_batch(const void* bag_desc, const void* scores_desc, int B, int C, int k, const float* logit_scale, float* out,
+                           int* idx, void* stream);
+
+/* u [B, 512] fp32 = (1 / N_b) sum_n x_n / max(|x_n|, 1e-12) for every bag of the table (bf16 or fp32 rows, D == 512, B <= 64): one
+ * streaming pass, summed in two levels in a fixed order (no atomics: bit-reproducible, and a bag's row does not depend on its batch).
+ * workspace: vlsa_unit_mean_workspace_bytes(B), no initialisation needed. */
+size_t vlsa_unit_mean_workspace_bytes(int B);
+int vlsa_unit_mean_batch(const void* bag_desc, int B, int x_dtype, int D, void* workspace, float* u, void* stream);
+
+/* Backward of the zero-shot bag logits, logits[b, c] = exp(*logit_scale) * mean_{n in S_bc} T^_c . x^_n, in ONE launch:
+ *   dT [C, 512] = gradient w.r.t. the raw text features (through T^_c = T_c / tnorm_c, tnorm_c = max(|T_c|, 1e-12)),
+ *   dls [1]     = sum_bc G[b, c] logits[b, c] (nullable),
+ * from G = dL/dlogits [B, C].  1 <= k <= 32: S_bc = idx [B, C, k] of vlsa_topk_select_batch (the rows are gathered from the bag table and
+ * re-normalised; accumulated in bag-then-slot order); k <= 0 (mean over all patches): u [B, 512] of vlsa_unit_mean_batch instead.
+ * B <= 64, C <= VLSA_MAX_K, D == 512, bf16 or fp32 bags.  No atomics: two runs give the same bits. */
+int vlsa_zeroshot_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int C, int k, const int* idx, const float* u,
+                                 const float* G, const float* logits, const float* That, const float* tnorm, const float* logit_scale,
+                                 float* dT, float* dls, void* stream);
+
 /* out[n, :] = X[n, :] / max(|X[n, :]|, 1e-12) for ALL N patch rows, fp32 out [N, D] (the image_features the reference's
  * zero-shot forward returns, model/vlsa.py:188-189); bf16 or fp32 rows, 16-byte aligned, D % 8 == 0 (bf16) / % 4 (fp32). */
 int vlsa_normalize_many(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, float* out, void* stream);

@@ -149,6 +149,10 @@ _SIGNATURES = {
     "vlsa_topk_mean_ws": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "vlsa_topk_values": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vlsa_topk_mean_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vlsa_topk_select_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vlsa_unit_mean_workspace_bytes": (c_size_t, [c_int]),
+    "vlsa_unit_mean_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vlsa_zeroshot_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 10),
     "vlsa_normalize_many": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "vlsa_topk_mean": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p]),
     "vlsa_tt_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int]),

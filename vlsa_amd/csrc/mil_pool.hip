@@ -469,8 +469,11 @@ __global__ __launch_bounds__(256) void k_rowdot(const XT* __restrict__ X, int64_
 // Each thread keeps the k largest of its strided subset (sorted insertion in registers), the 256 lists are
 // merged by k rounds of workgroup-wide arg-max.  k >= N degenerates to the mean of all N.
 constexpr int kTopKMax = 32;
+// kIdx: also emit the winners' rows, idx_out[0 .. k_slots): descending score, ties to the lower row, -1 past min(k, N) (the
+// differentiable zero-shot route gathers them in its backward).  The pooled value is the same sum in the same order either way.
+template <bool kIdx = false>
 __device__ __forceinline__ void topk_mean_row(const float* __restrict__ s, int64_t N, int k, float scale_log2e_inv,
-                                              float* __restrict__ out_elem) {
+                                              float* __restrict__ out_elem, int* __restrict__ idx_out = nullptr, int k_slots = 0) {
     __shared__ float sval[256];
     __shared__ int sidx[256];
     __shared__ float red[4];
@@ -480,46 +483,109 @@ __device__ __forceinline__ void topk_mean_row(const float* __restrict__ s, int64
         for (int64_t n = tid; n < N; n += 256) a += s[n];
         a = block_sum_256(a, red);
         if (tid == 0) *out_elem = a / (float)N * scale_log2e_inv;
+        if constexpr (kIdx) {
+            // all N <= k <= 32 rows win: thread 0 orders them (selection by largest score, lowest row first among equals)
+            if (tid == 0) {
+                unsigned int used = 0u;
+                const int n_rows = (int)N;
+                for (int j = 0; j < k_slots; ++j) {
+                    int best = -1;
+                    float bv = 0.f;
+                    for (int n = 0; n < n_rows; ++n) {
+                        if ((used >> n) & 1u) continue;
+                        const float v = s[n];
+                        if (best < 0 || v > bv) {
+                            best = n;
+                            bv = v;
+                        }
+                    }
+                    if (best >= 0) used |= 1u << best;
+                    idx_out[j] = best;
+                }
+            }
+        }
         return;
     }
     float top[kTopKMax];
+    int topi[kIdx ? kTopKMax : 1];
 #pragma unroll
     for (int i = 0; i < kTopKMax; ++i) top[i] = -INFINITY;
+    if constexpr (kIdx) {
+#pragma unroll
+        for (int i = 0; i < kTopKMax; ++i) topi[i] = 0x7fffffff;
+    }
     for (int64_t n = tid; n < N; n += 256) {
         float v = s[n];
         // sorted insertion (descending); static indices only
+        if constexpr (kIdx) {
+            int vi = (int)n;                 // rows come in ascending order: an equal score stays behind the earlier row
 #pragma unroll
-        for (int i = 0; i < kTopKMax; ++i) {
-            if (i < k) {
-                const float hi = fmaxf(top[i], v);
-                v = fminf(top[i], v);
-                top[i] = hi;
+            for (int i = 0; i < kTopKMax; ++i) {
+                if (i < k) {
+                    const bool up = v > top[i];
+                    const float hi = up ? v : top[i], lo = up ? top[i] : v;
+                    const int hii = up ? vi : topi[i], loi = up ? topi[i] : vi;
+                    top[i] = hi;
+                    topi[i] = hii;
+                    v = lo;
+                    vi = loi;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < kTopKMax; ++i) {
+                if (i < k) {
+                    const float hi = fmaxf(top[i], v);
+                    v = fminf(top[i], v);
+                    top[i] = hi;
+                }
             }
         }
     }
+    __shared__ int srow[kIdx ? 256 : 1];
     float sum = 0.f;
     int head = 0;  // position of this thread's best remaining candidate
     for (int round = 0; round < k; ++round) {
         float mine = -INFINITY;
+        int mine_row = 0x7fffffff;
 #pragma unroll
         for (int i = 0; i < kTopKMax; ++i)
-            if (i == head) mine = top[i];
+            if (i == head) {
+                mine = top[i];
+                if constexpr (kIdx) mine_row = topi[i];
+            }
         sval[tid] = mine;
         sidx[tid] = tid;
+        if constexpr (kIdx) srow[tid] = mine_row;
         __syncthreads();
         for (int off = 128; off > 0; off >>= 1) {
-            if (tid < off && sval[tid + off] > sval[tid]) {
-                sval[tid] = sval[tid + off];
-                sidx[tid] = sidx[tid + off];
+            if constexpr (kIdx) {
+                if (tid < off && (sval[tid + off] > sval[tid] || (sval[tid + off] == sval[tid] && srow[tid + off] < srow[tid]))) {
+                    sval[tid] = sval[tid + off];
+                    sidx[tid] = sidx[tid + off];
+                    srow[tid] = srow[tid + off];
+                }
+            } else {
+                if (tid < off && sval[tid + off] > sval[tid]) {
+                    sval[tid] = sval[tid + off];
+                    sidx[tid] = sidx[tid + off];
+                }
             }
             __syncthreads();
         }
         const int winner = sidx[0];
         sum += sval[0];
+        if constexpr (kIdx) {
+            if (tid == 0) idx_out[round] = srow[0];
+        }
         __syncthreads();
         if (tid == winner) ++head;
     }
     if (tid == 0) *out_elem = sum / (float)k * scale_log2e_inv;
+    if constexpr (kIdx) {
+        if (tid == 0)
+            for (int j = k; j < k_slots; ++j) idx_out[j] = -1;
+    }
 }
 __global__ __launch_bounds__(256) void k_topk_mean(const float* __restrict__ S, int64_t N, int k, float scale_log2e_inv,
                                                     float* __restrict__ out) {
@@ -528,18 +594,24 @@ __global__ __launch_bounds__(256) void k_topk_mean(const float* __restrict__ S, 
 }
 // B bags per launch: workgroup (class, bag) pools row `class` of bag's score matrix ([C, ld] fp32, e.g. the per-class cosines
 // the batched streaming kernel stored); k is clamped to the bag's N (k >= N: plain mean).  out [B, C] *= exp(*logit_scale).
+// kIdx (k_slots = the caller's k, 1 .. 32): idx [B, C, k_slots] gets the pooled rows of every (bag, class) as well.
+template <bool kIdx>
 __global__ __launch_bounds__(256) void k_topk_mean_batch(const vlsa_bag_desc* __restrict__ bags, const vlsa_rows_desc* __restrict__ sdesc,
                                                           int C, int k, const float* __restrict__ logit_scale,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, int* __restrict__ idx, int k_slots) {
     const int cls = blockIdx.x, bag = blockIdx.y;
     const int64_t N = bags[bag].N;
     const vlsa_rows_desc sd = sdesc[bag];
+    int* my_idx = kIdx ? idx + ((size_t)bag * C + cls) * k_slots : nullptr;
     if (N <= 0 || sd.ptr == nullptr) {
         if (threadIdx.x == 0) out[(size_t)bag * C + cls] = 0.f;
+        if constexpr (kIdx) {
+            if (threadIdx.x < k_slots) my_idx[threadIdx.x] = -1;
+        }
         return;
     }
     const float sc = logit_scale ? __expf(*logit_scale) : 1.f;
-    topk_mean_row(sd.ptr + (size_t)cls * sd.ld, N, k, sc, out + (size_t)bag * C + cls);
+    topk_mean_row<kIdx>(sd.ptr + (size_t)cls * sd.ld, N, k, sc, out + (size_t)bag * C + cls, my_idx, k_slots);
 }
 
 // Stage 1 of the two-stage top-k for long rows: workgroup (chunk b, class) keeps the k largest of ITS contiguous chunk of
@@ -675,6 +747,155 @@ __global__ __launch_bounds__(256) void k_rows_dot_relu(const float* __restrict__
     if (lane == 0) out[r] = resid != nullptr ? keep * resid[r] + (1.f - keep) * s : s;
 }
 
+
+// ---- the differentiable zero-shot route (identity FeatMIL + logit pooling with trainable prompts): the unit rows x^_n = x_n /
+// max(|x_n|, 1e-12) of a bag table, one wave per row of 512 columns, 8 columns per lane.  v[j] is column unit_col<XT>(lane, j).
+template <typename XT>
+__device__ __forceinline__ int unit_col(int lane, int j) {
+    if constexpr (sizeof(XT) == 2) return lane * 8 + j;
+    return (64 * (j >> 2) + lane) * 4 + (j & 3);
+}
+template <typename XT>
+__device__ __forceinline__ void load_row_512(const XT* __restrict__ row, int lane, float (&v)[8]) {
+    if constexpr (sizeof(XT) == 2) {
+        const u32x4 raw = *reinterpret_cast<const u32x4*>(row + lane * 8);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[2 * e] = __uint_as_float(raw[e] << 16);
+            v[2 * e + 1] = __uint_as_float(raw[e] & 0xffff0000u);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const f32x4 raw = *reinterpret_cast<const f32x4*>(row + (64 * c + lane) * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[4 * c + e] = raw[e];
+        }
+    }
+}
+__device__ __forceinline__ void unit_scale_512(float (&v)[8]) {
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += v[j] * v[j];
+    ss = wave_sum(ss);
+    const float inv = 1.f / fmaxf(sqrtf(ss), kNormEps);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] *= inv;
+}
+template <typename XT>
+__device__ __forceinline__ void unit_row_512(const XT* __restrict__ row, int lane, float (&v)[8]) {
+    load_row_512<XT>(row, lane, v);
+    unit_scale_512(v);
+}
+
+// u_b = (1 / N_b) sum_n x^_n, level one: work item (bag, part) -- kUnitParts contiguous row ranges per bag, a function of N_b alone, so
+// a bag's result does not depend on its batch -- is summed by one workgroup: wave w takes rows w, w + 4, ... of the range in order,
+// the four waves' sums are added in wave order.  A grid-stride walk over the B * kUnitParts items; no atomics anywhere.
+constexpr int kUnitParts = 32;
+template <typename XT>
+__global__ __launch_bounds__(256) void k_unit_mean_partial(const vlsa_bag_desc* __restrict__ bags, int B, float* __restrict__ part) {
+    __shared__ float comb[4][512];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int item = blockIdx.x; item < B * kUnitParts; item += gridDim.x) {
+        const vlsa_bag_desc d = bags[item / kUnitParts];
+        int64_t r0, r1;
+        rows_of_block(d.N > 0 ? d.N : 0, item % kUnitParts, kUnitParts, r0, r1);
+        const XT* X = static_cast<const XT*>(d.X);
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int64_t r = r0 + w; r < r1; r += 8) {      // two of the wave's rows in flight, added in row order
+            float v[8], v2[8];
+            const bool two = r + 4 < r1;
+            load_row_512<XT>(X + r * d.ldx, lane, v);
+            if (two) load_row_512<XT>(X + (r + 4) * d.ldx, lane, v2);
+            unit_scale_512(v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += v[j];
+            if (two) {
+                unit_scale_512(v2);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += v2[j];
+            }
+        }
+        __syncthreads();       // the previous item's reads of comb
+#pragma unroll
+        for (int j = 0; j < 8; ++j) comb[w][unit_col<XT>(lane, j)] = acc[j];
+        __syncthreads();
+        for (int c = tid; c < 512; c += 256) part[(size_t)item * 512 + c] = ((comb[0][c] + comb[1][c]) + comb[2][c]) + comb[3][c];
+    }
+}
+// level two: the kUnitParts partial rows of a bag in part order, over N_b
+__global__ __launch_bounds__(256) void k_unit_mean_finish(const vlsa_bag_desc* __restrict__ bags, const float* __restrict__ part,
+                                                           float* __restrict__ u) {
+    const int bag = blockIdx.x;
+    const int64_t N = bags[bag].N;
+    for (int c = threadIdx.x; c < 512; c += 256) {
+        float s = 0.f;
+        for (int g = 0; g < kUnitParts; ++g) s += part[((size_t)bag * kUnitParts + g) * 512 + c];
+        u[(size_t)bag * 512 + c] = N > 0 ? s / (float)N : 0.f;
+    }
+}
+
+// Backward of logits[b, c] = s * mean_{n in S_bc} T^_c . x^_n (s = exp(*logit_scale)) for all bags of a table: workgroup c owns class c.
+//   k > 0: the <= B * k pooled rows idx[b, c, :] are gathered from the bag table, re-normalised, and G[b, c] / m_b * x^_n (m_b =
+//          min(k, N_b)) is accumulated -- the (bag, slot) list is walked in order, entry j by wave j % 8, the eight waves' sums are
+//          added in wave order;  k == 0 (mean over all patches): sum_b G[b, c] u_b from the unit-row means, bags in order.
+//   epilogue: dT^_c = s * that sum;  dT_c = (dT^_c - (dT^_c . T^_c) T^_c) / tnorm_c;  workgroup 0 also writes
+//          d logit_scale = sum_{b, c} G[b, c] logits[b, c] (all C classes of the call: nothing is left to add up between launches).
+template <typename XT>
+__global__ __launch_bounds__(512) void k_zeroshot_backward(const vlsa_bag_desc* __restrict__ bags, int B, int C, int k,
+                                                            const int* __restrict__ idx, const float* __restrict__ u,
+                                                            const float* __restrict__ G, const float* __restrict__ logits,
+                                                            const float* __restrict__ That, const float* __restrict__ tnorm,
+                                                            const float* __restrict__ logit_scale, float* __restrict__ dT,
+                                                            float* __restrict__ dls) {
+    __shared__ float comb[8][512];
+    __shared__ float red[8];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cls = blockIdx.x;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (k > 0) {
+        for (int j = w; j < B * k; j += 8) {
+            const int b = j / k;
+            const int n = idx[((size_t)b * C + cls) * k + (j - b * k)];
+            const vlsa_bag_desc d = bags[b];
+            if (n < 0 || (int64_t)n >= d.N) continue;       // an empty slot (N_b < k)
+            const float g = G[(size_t)b * C + cls] / (float)(d.N < (int64_t)k ? (int)d.N : k);
+            float v[8];
+            unit_row_512<XT>(static_cast<const XT*>(d.X) + (int64_t)n * d.ldx, lane, v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = fmaf(g, v[i], acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) comb[w][unit_col<XT>(lane, i)] = acc[i];
+    } else {
+        for (int b = w; b < B; b += 8) {
+            const float g = G[(size_t)b * C + cls];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = fmaf(g, u[(size_t)b * 512 + lane * 8 + i], acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) comb[w][lane * 8 + i] = acc[i];
+    }
+    __syncthreads();
+    float dth = comb[0][tid];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) dth += comb[i][tid];
+    dth *= __expf(*logit_scale);
+    const float th = That[(size_t)cls * 512 + tid];
+    float dot = wave_sum(dth * th);
+    if (lane == 0) red[w] = dot;
+    __syncthreads();
+    dot = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
+    dT[(size_t)cls * 512 + tid] = (dth - dot * th) / tnorm[cls];
+    if (cls == 0 && dls != nullptr) {
+        float a = 0.f;
+        for (int i = tid; i < B * C; i += 512) a = fmaf(G[i], logits[i], a);
+        a = wave_sum(a);
+        __syncthreads();       // red is read above
+        if (lane == 0) red[w] = a;
+        __syncthreads();
+        if (tid == 0) *dls = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
+    }
+}
 }  // namespace vlsa
 
 using namespace vlsa;
@@ -891,8 +1112,66 @@ extern "C" int vlsa_topk_mean_batch(const void* bag_desc, const void* scores_des
     if (!bag_desc || !scores_desc || !out || B < 1 || C < 1) return VLSA_EINVAL;
     if (k > kTopKMax) return VLSA_EUNSUPPORTED;
     const int kk = k <= 0 ? 0x7fffffff : k;      // mean over all patches
-    hipLaunchKernelGGL(k_topk_mean_batch, dim3(C, B), dim3(256), 0, (hipStream_t)stream, static_cast<const vlsa_bag_desc*>(bag_desc),
-                       static_cast<const vlsa_rows_desc*>(scores_desc), C, kk, logit_scale, out);
+    hipLaunchKernelGGL(k_topk_mean_batch<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, static_cast<const vlsa_bag_desc*>(bag_desc),
+                       static_cast<const vlsa_rows_desc*>(scores_desc), C, kk, logit_scale, out, (int*)nullptr, 0);
+    return st();
+}
+
+// The same launch for the differentiable zero-shot route: out is bit-equal to vlsa_topk_mean_batch's, and for 1 <= k <= 32
+// idx [B, C, k] (int32) names the pooled rows of every (bag, class): descending score, ties to the lower row, -1 where N_b < k.
+// k <= 0 (mean over all patches): no index is written, idx may be NULL.
+extern "C" int vlsa_topk_select_batch(const void* bag_desc, const void* scores_desc, int B, int C, int k, const float* logit_scale,
+                                      float* out, int* idx, void* stream) {
+    if (!bag_desc || !scores_desc || !out || B < 1 || C < 1 || (k > 0 && !idx)) return VLSA_EINVAL;
+    if (k > kTopKMax) return VLSA_EUNSUPPORTED;
+    const vlsa_bag_desc* bd = static_cast<const vlsa_bag_desc*>(bag_desc);
+    const vlsa_rows_desc* sd = static_cast<const vlsa_rows_desc*>(scores_desc);
+    if (k <= 0)
+        hipLaunchKernelGGL(k_topk_mean_batch<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, bd, sd, C, 0x7fffffff, logit_scale, out,
+                           (int*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(k_topk_mean_batch<true>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, bd, sd, C, k, logit_scale, out, idx, k);
+    return st();
+}
+
+extern "C" size_t vlsa_unit_mean_workspace_bytes(int B) { return (size_t)(B < 1 ? 1 : B) * kUnitParts * 512 * sizeof(float); }
+
+// u [B, 512] = the mean unit row of every bag of the table (bf16 or fp32 rows, D == 512); workspace: vlsa_unit_mean_workspace_bytes(B).
+extern "C" int vlsa_unit_mean_batch(const void* bag_desc, int B, int x_dtype, int D, void* workspace, float* u, void* stream) {
+    if (!bag_desc || !workspace || !u || B < 1 || B > 64) return VLSA_EINVAL;
+    if (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32) return VLSA_EINVAL;
+    if (D != 512) return VLSA_EUNSUPPORTED;
+    const vlsa_bag_desc* bd = static_cast<const vlsa_bag_desc*>(bag_desc);
+    float* part = static_cast<float*>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const int items = B * kUnitParts, grid = items < 2048 ? items : 2048;
+    if (x_dtype == VLSA_DT_BF16)
+        hipLaunchKernelGGL(k_unit_mean_partial<__bf16>, dim3(grid), dim3(256), 0, s, bd, B, part);
+    else
+        hipLaunchKernelGGL(k_unit_mean_partial<float>, dim3(grid), dim3(256), 0, s, bd, B, part);
+    hipLaunchKernelGGL(k_unit_mean_finish, dim3(B), dim3(256), 0, s, bd, part, u);
+    return st();
+}
+
+// dT [C, 512] and d logit_scale [1] (nullable) of the zero-shot bag logits [B, C] in ONE launch (k_zeroshot_backward): k in 1 .. 32
+// with idx [B, C, k] from vlsa_topk_select_batch, or k <= 0 (mean over all patches) with u [B, 512] from vlsa_unit_mean_batch.
+extern "C" int vlsa_zeroshot_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int C, int k, const int* idx, const float* u,
+                                            const float* G, const float* logits, const float* That, const float* tnorm,
+                                            const float* logit_scale, float* dT, float* dls, void* stream) {
+    if (!bag_desc || !G || !logits || !That || !tnorm || !logit_scale || !dT || B < 1 || B > 64 || C < 1 || C > VLSA_MAX_K)
+        return VLSA_EINVAL;
+    if ((k > 0 && !idx) || (k <= 0 && !u)) return VLSA_EINVAL;
+    if (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32) return VLSA_EINVAL;
+    if (D != 512 || k > kTopKMax) return VLSA_EUNSUPPORTED;
+    const vlsa_bag_desc* bd = static_cast<const vlsa_bag_desc*>(bag_desc);
+    const int kk = k > 0 ? k : 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (x_dtype == VLSA_DT_BF16)
+        hipLaunchKernelGGL(k_zeroshot_backward<__bf16>, dim3(C), dim3(512), 0, s, bd, B, C, kk, idx, u, G, logits, That, tnorm, logit_scale,
+                           dT, dls);
+    else
+        hipLaunchKernelGGL(k_zeroshot_backward<float>, dim3(C), dim3(512), 0, s, bd, B, C, kk, idx, u, G, logits, That, tnorm, logit_scale,
+                           dT, dls);
     return st();
 }
 

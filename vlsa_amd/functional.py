@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from ._native import VlsaNativeError
@@ -704,25 +705,40 @@ def choose_groups(sizes, reserved_cus: int = 0) -> int:
 class AttnBuffers:
     """One fp32 [P, ld_i] matrix per bag of a batch (ld_i = N_i rounded up to 64) in ONE allocation, plus the device-side
     ``vlsa_rows_desc`` table the batched kernels take.  The streaming kernel stores the log2-domain scores there and
-    ``vlsa_attn_normalise_batch`` turns them into the attention weights in place; ``views[i]`` is bag i's A [P, N_i]."""
+    ``vlsa_attn_normalise_batch`` turns them into the attention weights in place; ``views[i]`` is bag i's A [P, N_i].
+    ``bag_desc``: the bags' descriptor table, already on the device -- inside a graph capture the ``vlsa_rows_desc`` table is then
+    derived from it by in-stream ops (``_layout``, the same arithmetic) instead of being staged from the host, which a capture
+    cannot hold; there is no ``ndesc`` in that case (``bag_desc`` itself carries the N_i)."""
 
-    def __init__(self, sizes, P: int, device):
+    @staticmethod
+    def _layout(n, P: int):
+        """(ld_i, first float of bag i's matrix, floats in all) for the N_i in ``n``: a numpy array or a device tensor (int64)"""
+        ld = (n + 63) // 64 * 64
+        end = (P * ld).cumsum(0)
+        return ld, end - P * ld, end
+
+    def __init__(self, sizes, P: int, device, bag_desc: Optional[torch.Tensor] = None):
         self.sizes, self.P = [int(n) for n in sizes], int(P)
         B = len(self.sizes)
         n = np.asarray(self.sizes, dtype=np.int64)
-        lds = (n + 63) // 64 * 64
-        offs = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(P * lds, out=offs[1:])
+        lds, start, end = self._layout(n, P)
+        offs = np.concatenate([start, end[-1:]]) if B else np.zeros(1, dtype=np.int64)
         self.buf = torch.empty(max(int(offs[B]), 4), dtype=torch.float32, device=device)
         base = self.buf.data_ptr()
-        # ONE upload: [B, 2] vlsa_rows_desc (pointer, pitch) followed by a [B, 3] bag table holding only the N_i (vlsa_bag_desc
-        # layout: lets the normalise launch outlive a later set_bags())
-        host = np.zeros(5 * B, dtype=np.int64)
-        host[0:2 * B:2] = np.where(n > 0, base + 4 * offs[:B], 0)
-        host[1:2 * B:2] = lds
-        host[2 * B + 1::3] = n
-        dev = _stage_table(host, device, "AttnBuffers")
-        self.desc, self.ndesc = dev[:2 * B].view(B, 2), dev[2 * B:].view(B, 3)
+        if bag_desc is not None and torch.cuda.is_current_stream_capturing():
+            dn = bag_desc[:, 1]
+            dld, dstart, _ = self._layout(dn, P)
+            self.desc = torch.stack([torch.where(dn > 0, dstart * 4 + base, torch.zeros_like(dn)), dld], 1).contiguous()
+            self.ndesc = None
+        else:
+            # ONE upload: [B, 2] vlsa_rows_desc (pointer, pitch) followed by a [B, 3] bag table holding only the N_i (vlsa_bag_desc
+            # layout: lets the normalise launch outlive a later set_bags())
+            host = np.zeros(5 * B, dtype=np.int64)
+            host[0:2 * B:2] = np.where(n > 0, base + 4 * offs[:B], 0)
+            host[1:2 * B:2] = lds
+            host[2 * B + 1::3] = n
+            dev = _stage_table(host, device, "AttnBuffers")
+            self.desc, self.ndesc = dev[:2 * B].view(B, 2), dev[2 * B:].view(B, 3)
         self._offs, self._lds = offs, lds
         self._views = None
         self.max_n = max(self.sizes) if self.sizes else 0
@@ -1800,32 +1816,101 @@ class VlfanBatchPlan:
                   "vlfan_partial_batch")
 
 
-def zeroshot_pool_bags(bags, T: torch.Tensor, logit_scale: torch.Tensor, k: Optional[int]) -> torch.Tensor:
-    """Zero-shot bag logits [B, K] for a list of up to 64 bags (bf16 or fp32 [N_i, 512], one dtype): the K text features go
-    through the persistent multi-bag streaming kernel as queries (scale 1 / log2(e): the stored scores ARE the cosines), then
-    ONE launch pools every (class, bag) row (top-k mean, k clamped to N_i; None: mean).  model/vlsa.py:185-196 per bag."""
-    _need_gpu(T, logit_scale, *bags)
+def _zeroshot_launches(table, T: torch.Tensor, ls: torch.Tensor, k: Optional[int], want_idx: bool):
+    """The launches both routes of ``zeroshot_pool_bags`` share, per chunk of <= MAX_P classes: query preparation, the persistent
+    streaming kernel storing the per-class cosines, one pooling launch (vlsa_topk_mean_batch, or its index-emitting sibling
+    vlsa_topk_select_batch: the same pooled values bit for bit).  The [K, N] cosines are dropped after each chunk's pooling.
+    -> (pooled [B, K] times exp(ls), idx [B, K, k] int32 or None, prepared query blocks)"""
     lib, s = nat.load(), _stream()
-    K = T.shape[0]
-    table = _BagTable(bags)
-    B, dev = table.B, table.desc.device
-    out = torch.empty(B, K, dtype=torch.float32, device=dev)
-    sizes = table.sizes
-    ls = _f32c(logit_scale).reshape(1)
+    K, B, dev = T.shape[0], table.B, table.desc.device
+    kk = 0 if k is None else int(k)
+    vals, idxs, qps = [], [], []
     for k0 in range(0, K, nat.MAX_P):
-        Tk = T[k0:k0 + nat.MAX_P]
-        Pk = Tk.shape[0]
-        qp = prepare_queries(Tk, False, 1.0 / 1.4426950408889634)
-        sc = AttnBuffers(sizes, Pk, dev)
+        qp = prepare_queries(T[k0:k0 + nat.MAX_P], False, 1.0 / 1.4426950408889634)
+        Pk = qp.P
+        sc = AttnBuffers(table.sizes, Pk, dev, bag_desc=table.desc)
         ws = torch.empty(lib.vlsa_batch_workspace_bytes(B, Pk, table.D), dtype=torch.uint8, device=dev)
         nat.check(lib.vlsa_vlfan_partial_batch_scores(_p(table.desc), B, table.dt, table.D, _p(qp.buf), Pk, _p(ws), 0,
                                                       table.groups(0), _p(sc.desc), s), "vlsa_vlfan_partial_batch_scores")
-        part = out if (k0 == 0 and Pk == K) else torch.empty(B, Pk, dtype=torch.float32, device=dev)
-        nat.check(lib.vlsa_topk_mean_batch(_p(table.desc), _p(sc.desc), B, Pk, 0 if k is None else int(k), _p(ls), _p(part), s),
-                  "vlsa_topk_mean_batch")
-        if part is not out:
-            out[:, k0:k0 + Pk] = part
-    return out
+        part = torch.empty(B, Pk, dtype=torch.float32, device=dev)
+        if want_idx:
+            idx = torch.empty(B, Pk, kk, dtype=torch.int32, device=dev) if kk else None
+            nat.check(lib.vlsa_topk_select_batch(_p(table.desc), _p(sc.desc), B, Pk, kk, _p(ls), _p(part), _p(idx), s),
+                      "vlsa_topk_select_batch")
+            idxs.append(idx)
+        else:
+            nat.check(lib.vlsa_topk_mean_batch(_p(table.desc), _p(sc.desc), B, Pk, kk, _p(ls), _p(part), s), "vlsa_topk_mean_batch")
+        vals.append(part)
+        qps.append(qp)
+    one = len(vals) == 1
+    idx = None if not (want_idx and kk) else (idxs[0] if one else torch.cat(idxs, 1))
+    return (vals[0] if one else torch.cat(vals, 1)), idx, qps
+
+
+class _ZeroshotPoolFn(torch.autograd.Function):
+    """Zero-shot bag logits [B, K] of a chunk of <= 64 bags as ONE autograd node, differentiable w.r.t. the text features T and the
+    logit scale (the bags carry no gradient).  Forward: the launches of the no-grad route (``_zeroshot_launches``) with the pooled rows'
+    indices kept, and vlsa_unit_mean_batch for the mean over all patches; idx (or the unit-row means), the logits, T^ and the bag
+    table are what the backward needs.  Backward: vlsa_zeroshot_backward_batch, one launch.  Also returns T^ [K, 512]."""
+
+    @staticmethod
+    def forward(ctx, T, logit_scale, k, table, *bag_tensors):
+        lib = nat.load()
+        B, dev = table.B, table.desc.device
+        ls = _f32c(logit_scale).reshape(1)
+        logits, sel, qps = _zeroshot_launches(table, _f32c(T), ls, k, True)
+        That = qps[0].qhat if len(qps) == 1 else torch.cat([q.qhat for q in qps], 0)
+        tnorm = qps[0].qnorm if len(qps) == 1 else torch.cat([q.qnorm for q in qps], 0)
+        if k is None:
+            sel = torch.empty(B, 512, dtype=torch.float32, device=dev)       # u_b: the mean unit row of every bag
+            uws = torch.empty(lib.vlsa_unit_mean_workspace_bytes(B), dtype=torch.uint8, device=dev)
+            nat.check(lib.vlsa_unit_mean_batch(_p(table.desc), B, table.dt, table.D, _p(uws), _p(sel), _stream()), "vlsa_unit_mean_batch")
+        ctx.save_for_backward(sel, logits, That, tnorm, ls)
+        ctx.table, ctx.k, ctx.bags = table, k, bag_tensors      # the kernels read the bags through the descriptor table
+        ctx.shapes, ctx.dtypes = (T.shape, logit_scale.shape), (T.dtype, logit_scale.dtype)
+        ctx.set_materialize_grads(False)
+        return logits, That
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlogits, g_That):
+        sel, logits, That, tnorm, ls = ctx.saved_tensors
+        table, k = ctx.table, ctx.k
+        K = That.shape[0]
+        dT = dls = None
+        if dlogits is not None:         # ONE launch writes both gradients, whichever of them autograd asked for
+            g = _f32c(dlogits)
+            dT = torch.empty(K, 512, dtype=torch.float32, device=That.device)
+            dls = torch.empty(1, dtype=torch.float32, device=That.device)
+            nat.check(nat.load().vlsa_zeroshot_backward_batch(_p(table.desc), table.B, table.dt, table.D, K, 0 if k is None else int(k),
+                                                              None if k is None else _p(sel), _p(sel) if k is None else None, _p(g),
+                                                              _p(logits), _p(That), _p(tnorm), _p(ls), _p(dT), _p(dls), _stream()),
+                      "vlsa_zeroshot_backward_batch")
+            dls = dls.reshape(ctx.shapes[1]).to(ctx.dtypes[1])
+        if g_That is not None:          # somebody differentiates the returned unit text features: K rows, torch ops
+            gt = g_That.float()
+            gt = (gt - (gt * That).sum(1, keepdim=True) * That) / tnorm[:, None]
+            dT = gt if dT is None else dT + gt
+        if dT is not None:
+            dT = dT.reshape(ctx.shapes[0]).to(ctx.dtypes[0])
+        return (dT, dls, None, None, *([None] * len(ctx.bags)))
+
+
+def zeroshot_pool_bags(bags, T: torch.Tensor, logit_scale: torch.Tensor, k: Optional[int], return_text: bool = False):
+    """Zero-shot bag logits [B, K] for a list of up to 64 bags (bf16 or fp32 [N_i, 512], one dtype): the K text features go
+    through the persistent multi-bag streaming kernel as queries (scale 1 / log2(e): the stored scores ARE the cosines), then
+    ONE launch pools every (class, bag) row (top-k mean, k clamped to N_i; None: mean).  model/vlsa.py:185-196 per bag.
+    With grad enabled and T or logit_scale requiring it, the same launches run as one autograd node (``_ZeroshotPoolFn``: the same
+    logits bit for bit, gradients for T and logit_scale, none for the bags -- a bag that requires grad is refused).
+    return_text: -> (logits, T^ [K, 512]), T^ carrying the graph to T on the differentiable route."""
+    _need_gpu(T, logit_scale, *bags)
+    if torch.is_grad_enabled() and (T.requires_grad or logit_scale.requires_grad):
+        _no_bag_grad(*bags)
+        table = _BagTable(bags)
+        logits, That = _ZeroshotPoolFn.apply(T, logit_scale, k, table, *table.bags)
+        return (logits, That) if return_text else logits
+    out, _, _ = _zeroshot_launches(_BagTable(bags), T, _f32c(logit_scale).reshape(1), k, False)
+    return (out, normalize_rows(T)[0]) if return_text else out
 
 
 def query_pool_attention(rows: torch.Tensor, module) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -708,8 +708,9 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return None
         enc = self.mil_encoder
         if isinstance(enc, FeatMIL) and enc.pooling not in ("mean", "max"):
-            # identity FeatMIL (zero-shot logit pooling with trainable prompts): the reference returns the bag's [N, D] patch features
-            # as its second output (model/vlsa.py:188-196) -- a deferred batch hands out ONE row per bag, so these calls run as they come
+            # identity FeatMIL (zero-shot logit pooling with trainable prompts): the per-bag call returns the bag's [N, D] patch
+            # features as its second output (model/vlsa.py:188-196) -- a deferred batch hands out ONE row per bag, so per-bag calls run
+            # as they come, through torch ops.  The batched HIP route of this stage is ``forward_bags`` (``_forward_bags_zeroshot_train``).
             return None
         if not isinstance(enc, (VLFAN, FeatMIL, mil_encoders.DeepMIL)):
             return None                                      # an encoder this package does not know: no claim about its output shape
@@ -928,10 +929,38 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
                 return self.logit_scale.exp() * image_features @ text_n.t(), image_features, text_n
             if isinstance(enc, mil_encoders.DeepMIL) and len(bags) > 0:
                 return self._deepmil_logits(enc.forward_bags(bags), text_features)
+            if isinstance(enc, FeatMIL) and enc.pooling not in ("mean", "max") and len(bags) > 0:
+                routed = self._forward_bags_zeroshot_train(bags, text_features)
+                if routed is not None:
+                    return routed
             outs = [self.forward(x if x.dim() == 3 else x[None]) for x in bags]
             return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), outs[0][2]
         with torch.no_grad():
             return self._forward_bags_fused(bags, text_features)
+
+    def _forward_bags_zeroshot_train(self, bags, text_features):
+        """Identity FeatMIL + logit pooling with a gradient to the text side (the prompt pre-training stage: trainable CoOp prompts
+        and / or logit scale, cfg_zero_shot_conch.yaml): per chunk of 64 bags the launches of ``_forward_bags_zeroshot`` as ONE
+        autograd node whose backward is one launch (``VF.zeroshot_pool_bags``).  Returns (logits [B, K], patch features as
+        ``_forward_bags_zeroshot`` hands them out, T^ [K, 512] with the graph to the prompts); None: not this route's case (bags of
+        several dtypes / another width / with a gradient of their own, more than 64 classes) -- the bag-by-bag calls serve it."""
+        from .deepmil import _parse_logit_pooling
+        T, ls = text_features, self.logit_scale
+        if not (T.is_cuda and T.dim() == 2 and 1 <= T.shape[0] <= 64 and T.shape[1] == 512 and ls.is_cuda):
+            return None
+        bagset = bags if isinstance(bags, VF.BagSet) and bags.D == 512 else None
+        flat = bagset if bagset is not None else [VF._bag2d(x) for x in bags]
+        if bagset is None and not all(x.is_cuda and x.dtype == flat[0].dtype and x.dtype in (torch.bfloat16, torch.float32)
+                                      and x.shape[1] == 512 and x.shape[0] > 0 and not x.requires_grad for x in flat):
+            return None
+        k = _parse_logit_pooling(self.image_encoder_cfg["pooling"])
+        if k is not None and not (1 <= k <= 32):
+            return None
+        outs = [VF.zeroshot_pool_bags(bagset.chunk(i, 64) if bagset is not None else flat[i:i + 64], T, ls, k, return_text=True)
+                for i in range(0, len(flat), 64)]
+        logits = outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs])
+        feats = [VF.normalize_many(x) for x in flat] if getattr(self, "return_patch_features", None) is True else None
+        return logits, feats, outs[0][1]
 
     def _deepmil_logits(self, feats, text_features):
         """cosine logits of a DeepMIL batch's bag vectors [B, C], as the per-bag ``forward`` forms them: both normalisations and the
