@@ -781,6 +781,39 @@ int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtype, int D, i
                               const int64_t* seed_word, const float* state, void* ws, float* dWc, float* dbc, float* dWq, float* dbq,
                               float* dWv, float* dbv, float* dWf, float* dbf, void* stream);
 
+/* ---- DeepAttnMISL's cluster layer (model/deepmil.py:565-577) over a table of bags -------------------------------------------------
+ * pre_n = Wp x_n + bp, h_n = relu(pre_n), hc_k = mean of h_n over the rows whose cluster id is k (csrc/cluster_pool.hip): one streaming
+ * MFMA kernel whose h never reaches memory, and a merge of its per-workgroup records in a fixed order (no float atomics).
+ *   bag_desc   device table of B vlsa_bag_desc (1 <= B <= 64, bf16 or fp32 rows, one dtype).  D == 512, H == 256, 1 <= Kc <= 16:
+ *              VLSA_EUNSUPPORTED otherwise.  bf16 rows are consumed exactly against a three-term bf16 split of Wp; fp32 rows take the
+ *              fp32-input MFMA on Wp as it is.
+ *   part_start [B + 1] int32 (device): bag b owns the partial records part_start[b] .. part_start[b + 1], vlsa_cluster_pool_parts(N_b)
+ *              of them -- a function of N_b alone (tiles of vlsa_cluster_pool_tile_rows() rows, at most 128 parts), so a bag's hc is
+ *              bit-equal alone and in a batch; n_parts = part_start[B].
+ *   row_off    [B] int64 (device): first row of bag b among the launch's rows laid back to back; ids and mask are indexed that way.
+ *   ids        [sum N_b] int32 cluster id per row; a row whose id is outside [0, Kc) belongs to no cluster.
+ *   Wp [256][512], bp [256]  phis.0 (the 1x1 convolution as a matrix).
+ *   ws         scratch of vlsa_cluster_pool_workspace_bytes(n_parts, Kc); nothing in it outlives a call.
+ *   hc [B][Kc][256] fp32 (an empty cluster's row is zero), cnt [B][Kc] int32.
+ *   mask       (nullable) [sum N_b][8] uint32: bit j of a row set iff pre_n[j] > 0 -- what the backward reads.
+ * vlsa_cluster_pool_backward_batch: dWp [256][512] and dbp [256] of sum_b dhc[b] . hc[b] over all rows of all bags of the launch, with
+ *   dpre_n = mask_n * dhc[b(n)][c_n] / cnt[b(n)][c_n] (the mask READ, not recomputed); the rows receive no gradient.
+ *   tile_start [B + 1] int32 (device): first row tile of every bag in tiles of vlsa_cluster_pool_backward_tile_rows() rows,
+ *              n_tiles = tile_start[B].  dWp accumulates in registers per (hidden slice of 64, row split); the R = min(64,
+ *              ceil(n_tiles / 4)) split partials -- ws: vlsa_cluster_pool_backward_workspace_bytes(n_tiles) = R * (256 * 512 + 256) * 4
+ *              bytes, at most 32.1 MiB -- are added in split order: bit-reproducible run to run. */
+int vlsa_cluster_pool_tile_rows(void);
+int vlsa_cluster_pool_parts(int64_t N);
+size_t vlsa_cluster_pool_workspace_bytes(int n_parts, int Kc);
+int vlsa_cluster_pool_backward_tile_rows(void);
+size_t vlsa_cluster_pool_backward_workspace_bytes(int n_tiles);
+int vlsa_cluster_pool_forward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int Kc, const int* part_start, int n_parts,
+                                    const int64_t* row_off, const int* ids, const float* Wp, const float* bp, void* ws, float* hc,
+                                    int* cnt, uint32_t* mask, void* stream);
+int vlsa_cluster_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int Kc, const int* tile_start, int n_tiles,
+                                     const int64_t* row_off, const int* ids, const uint32_t* mask, const float* dhc, const int* cnt,
+                                     void* ws, float* dWp, float* dbp, void* stream);
+
 /* Device-side descriptor tables of ONE bag for the *_backward entry points above (bag_desc [1], optional second table, row
  * offset [1], tile_start [2]) written from by-value arguments by a one-thread kernel: dst = 64 bytes of device memory.  Returns the
  * number of tiles (> 0) or a negative error code.  Layout: {X, N, ld} {extra, N, extra_ld}? {0} {int32 0, int32 n_tiles}. */

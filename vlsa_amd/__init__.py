@@ -5,4 +5,11 @@ in hand-written HIP kernels behind the C ABI of include/vlsa_hip.h.  There is no
 """
 from ._native import VlsaNativeError  # noqa: F401
 
-__all__ = ["VlsaNativeError"]
+__all__ = ["VlsaNativeError", "DeepAttnMISL"]
+
+
+def __getattr__(name):
+    if name == "DeepAttnMISL":          # imported on first use: the package itself needs no torch
+        from .deepmil import DeepAttnMISL
+        return DeepAttnMISL
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -196,6 +196,13 @@ _SIGNATURES = {
                                  + [c_float] + [c_void_p] * 7),
     "vlsa_dsmil_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4
                                   + [c_float] + [c_void_p] * 12),
+    "vlsa_cluster_pool_tile_rows": (c_int, []),
+    "vlsa_cluster_pool_parts": (c_int, [c_int64]),
+    "vlsa_cluster_pool_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vlsa_cluster_pool_backward_tile_rows": (c_int, []),
+    "vlsa_cluster_pool_backward_workspace_bytes": (c_size_t, [c_int]),
+    "vlsa_cluster_pool_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
+    "vlsa_cluster_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
     "vlsa_debug_probe": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),
     "vlsa_xchg_max_peers": (c_int, []),
     "vlsa_xchg_result_floats": (c_size_t, [c_int, c_int, c_int, c_void_p]),

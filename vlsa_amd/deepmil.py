@@ -660,3 +660,61 @@ class DSMIL(VF.nat.TransientCaches, nn.Module):
         if ret_attn:
             res[1] = res[1][0]
         return tuple(res)
+
+
+class DeepAttnMISL(nn.Module):
+    """DeepAttnMISL (Yao et al., MedIA 2020; model/deepmil.py:542-580) with the reference's constructor and state-dict keys
+    (``phis.0.*`` -- the 1x1 convolution, weight [256, 512, 1, 1] --, ``attention_net.0.*``, ``attention_net.3.{fc1.0, score.0, fc2}.*``,
+    ``output_layer.*``).
+
+    The reference gathers each cluster's rows, runs the convolution on them and pools; here ``phis`` and the per-cluster mean are ONE
+    HIP streaming pass over the bag (csrc/cluster_pool.hip: the [N, 256] activations never reach memory; an empty cluster gives a
+    zero row; an id outside [0, num_clusters) belongs to no cluster), forward and backward, for ``dim_in = 512``, ``dim_hid = 256``,
+    ``num_clusters <= 16``.  Everything behind it is ``num_clusters`` rows per bag and stays torch modules, batched over
+    [B, num_clusters, 256].  Gradients reach every parameter; the bag rows get none, and they must be finite.
+
+    The tail is EVALUATED IN FLOAT64 (float64 copies of its fp32 parameters through ``functional_call``, autocast switched off around
+    it; logits and gradients come back as fp32): the attention branch's gradients are differences of nearly equal cluster rows, 1e-7
+    .. 1e-10 of the others, which fp32 resolves to about 2e-3 of their largest entry only.  It is ``num_clusters`` rows per bag, so
+    the cost is a few small float64 launches; the modules, their dropout and their gradients are torch's own."""
+
+    def __init__(self, dim_in=512, dim_hid=256, num_cls=1, num_clusters=8, dropout=0.25, **kwargs):
+        super().__init__()
+        self.dim_hid = dim_hid
+        self.num_clusters = num_clusters
+        self.phis = nn.Sequential(nn.Conv2d(dim_in, dim_hid, 1), nn.ReLU())
+        self.pool1d = nn.AdaptiveAvgPool1d(1)
+        self.attention_net = nn.Sequential(nn.Linear(dim_hid, dim_hid), nn.ReLU(), nn.Dropout(dropout),
+                                           Gated_Attention_Pooling(dim_hid, dim_hid, dropout=dropout))
+        self.output_layer = nn.Linear(in_features=dim_hid, out_features=num_cls)
+
+    def cluster_features(self, bags, cluster_ids, ret_state=False):
+        """h_cluster [B, num_clusters, 256] of a list of bags (each [1, N_i, 512] or [N_i, 512]) in chunks of <= 64 per launch chain;
+        ret_state: also the cluster sizes [B, Kc] and the ReLU mask bits [sum N_i, 8] the backward reads"""
+        conv = self.phis._modules["0"]
+        Wp, bp, Kc = conv.weight, conv.bias, int(self.num_clusters)
+        if tuple(Wp.shape) != (256, 512, 1, 1) or bp is None or not (1 <= Kc <= 16):
+            raise VF.VlsaNativeError(f"DeepAttnMISL: the HIP kernels cover dim_in = 512, dim_hid = 256, num_clusters <= 16 (got "
+                                     f"{Wp.shape[1]}, {Wp.shape[0]}, {Kc}); there is no other route")
+        if len(bags) == 0 or len(bags) != len(cluster_ids):
+            raise ValueError("forward_bags needs at least one bag and one cluster-id tensor per bag")
+        out = [VF.cluster_pool_bags(bags[i:i + 64], cluster_ids[i:i + 64], Wp, bp, num_clusters=Kc, ret_state=ret_state)
+               for i in range(0, len(bags), 64)]
+        if not ret_state:
+            return out[0] if len(out) == 1 else torch.cat(out)
+        return tuple(o[0] if len(out) == 1 else torch.cat(o) for o in zip(*out))
+
+    def forward_bags(self, bags, cluster_ids, ret_state=False):
+        """logits [B, num_cls] of a list of bags and their cluster ids: ``torch.cat([self(x, c) for x, c in zip(bags, cluster_ids)])``"""
+        hc = self.cluster_features(bags, cluster_ids, ret_state)
+        state = hc[1:] if ret_state else ()
+        hc = hc[0] if ret_state else hc
+        # the tail in float64 (see the class docstring); autocast would take its products back down to 16 bits
+        with torch.autocast(device_type=hc.device.type, enabled=False):
+            tail = {k: p.double() for k, p in self.attention_net.named_parameters()}
+            H, _ = torch.func.functional_call(self.attention_net, tail, (hc.double(),))          # [B, 256], [B, Kc]
+            out = F.linear(H, self.output_layer.weight.double(), self.output_layer.bias.double()).to(hc.dtype)
+        return (out, hc, *state) if ret_state else out
+
+    def forward(self, X, cluster_id, *args):
+        return self.forward_bags([X], [cluster_id])

@@ -2021,3 +2021,115 @@ def dsmil_bags(bags, Wc, bc, Wq, bq, Wv, bv, Wf, bf, drop_p: float = 0.0, seed_w
     plan = DsmilBagsPlan.of(bags)
     logits, attn, crit = _DsmilBagsFn.apply(plan, drop_p, seed_word if drop_p else None, bool(want_attn), Wc, bc, Wq, bq, Wv, bv, Wf, bf, *bags)
     return logits, (attn if want_attn else None), crit
+
+
+# ---- DeepAttnMISL's cluster layer (model/deepmil.py:565-577): phi + per-cluster mean over a table of bags -------------------------
+def cluster_pool_part_counts(n: torch.Tensor) -> torch.Tensor:
+    """vlsa_cluster_pool_parts of every entry of an integer tensor of bag sizes, on the tensor's own device: the tile and the cap on
+    the parts are the library's (its answer for a bag of 2^62 rows), so the table and the launch's grid cannot drift apart"""
+    lib = nat.load()
+    tile, cap = int(lib.vlsa_cluster_pool_tile_rows()), int(lib.vlsa_cluster_pool_parts(1 << 62))
+    return torch.clamp(torch.div(n + (tile - 1), tile, rounding_mode="floor"), 1, cap)
+
+
+class ClusterPoolPlan(_ChunkPlan):
+    """Device tables of one chunk of <= 64 bags for vlsa_cluster_pool_forward_batch / _backward_batch: the descriptor table, the row
+    offsets, part_start [B + 1] (bag b owns vlsa_cluster_pool_parts(N_b) partial records -- a function of N_b alone) and the
+    backward's tile_start.  Derived from the descriptor table by in-stream ops on the device (a ``BagSet``'s table is already there; a
+    plain list's is staged from the host first); the tile and the cap on the parts are asked of the library, never restated here."""
+
+    def __init__(self, bags):
+        lib = nat.load()
+        super().__init__(_chunk_tables(bags, "the batched DeepAttnMISL route over a plain list of bags"))
+        self.n_parts = sum(int(lib.vlsa_cluster_pool_parts(n)) for n in self.sizes)
+        n = self.desc[:, 1]
+        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
+        self.part_start[1:] = torch.cumsum(cluster_pool_part_counts(n), 0)
+        self.ts_b, self.n_tiles_b = self.tables.tile_start(int(lib.vlsa_cluster_pool_backward_tile_rows()))
+
+
+class _ClusterPoolFn(torch.autograd.Function):
+    """hc [B, Kc, 256] of DeepAttnMISL's cluster layer over a chunk of <= 64 bags as ONE autograd node: three launches forward (weight
+    split, streaming product + per-cluster sums, merge), two backward.  The forward keeps the ReLU mask (256 bits per row) and the
+    cluster sizes; the backward reads them.  Gradients for Wp and bp, none for the bag rows."""
+
+    @staticmethod
+    def forward(ctx, plan, ids, Kc, want_mask, Wp, bp, *bag_tensors):
+        lib, s = nat.load(), _stream()
+        dev, B = plan.desc.device, plan.B
+        Wf, bf = _f32c(Wp).reshape(Wp.shape[0], -1), _f32c(bp)
+        ws = torch.empty(lib.vlsa_cluster_pool_workspace_bytes(plan.n_parts, Kc), dtype=torch.uint8, device=dev)
+        hc = torch.empty(B, Kc, 256, dtype=torch.float32, device=dev)
+        cnt = torch.empty(B, Kc, dtype=torch.int32, device=dev)
+        keep = want_mask or any(ctx.needs_input_grad[4:6])
+        mask = torch.empty(plan.total, 8, dtype=torch.int32, device=dev) if keep else None
+        nat.check(lib.vlsa_cluster_pool_forward_batch(_p(plan.desc), B, plan.dt, Wf.shape[1], Wf.shape[0], Kc, _p(plan.part_start), plan.n_parts,
+                                                      _p(plan.a_off), _p(ids), _p(Wf), _p(bf), _p(ws), _p(hc), _p(cnt), _p(mask), s),
+                  "vlsa_cluster_pool_forward_batch")
+        ctx.save_for_backward(ids, cnt, mask)
+        ctx.plan, ctx.Kc, ctx.shapes = plan, Kc, (Wp.shape, bp.shape)
+        ctx.bags = bag_tensors                        # the kernels read them through the descriptor table
+        if mask is None:
+            mask = cnt.new_empty(0, 8)
+        ctx.mark_non_differentiable(cnt, mask)
+        return hc, cnt, mask
+
+    @staticmethod
+    def backward(ctx, dhc, _dcnt, _dmask):
+        lib, s = nat.load(), _stream()
+        ids, cnt, mask = ctx.saved_tensors
+        plan, Kc = ctx.plan, ctx.Kc
+        dev, B = cnt.device, plan.B
+        g = _f32c(dhc)
+        ws = torch.empty(lib.vlsa_cluster_pool_backward_workspace_bytes(plan.n_tiles_b), dtype=torch.uint8, device=dev)
+        dW = torch.empty(256, 512, dtype=torch.float32, device=dev)
+        db = torch.empty(256, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_cluster_pool_backward_batch(_p(plan.desc), B, plan.dt, 512, 256, Kc, _p(plan.ts_b), plan.n_tiles_b, _p(plan.a_off),
+                                                       _p(ids), _p(mask), _p(g), _p(cnt), _p(ws), _p(dW), _p(db), s),
+                  "vlsa_cluster_pool_backward_batch")
+        return (None, None, None, None, dW.view(ctx.shapes[0]), db.view(ctx.shapes[1]), *([None] * len(ctx.bags)))
+
+
+def cluster_ids_int32(cluster_ids, sizes, device, Kc: int) -> torch.Tensor:
+    """per-bag cluster ids ([N_i] or [1, N_i], float or integer, CPU or GPU -- the reference's loader hands a CPU float tensor) as ONE
+    device int32 [sum N_i] in bag order.  An id that ``cluster_id == i`` matches for no i in [0, Kc) -- fractional, NaN, infinite,
+    negative, >= Kc, beyond int32 -- becomes -1 BEFORE the cast, so that no out-of-range conversion can land inside [0, Kc)."""
+    if len(cluster_ids) != len(sizes):
+        raise ValueError(f"{len(sizes)} bags but {len(cluster_ids)} cluster-id tensors")
+    out = []
+    for c, n in zip(cluster_ids, sizes):
+        c = torch.as_tensor(c).detach().reshape(-1)
+        if c.numel() != n:
+            raise ValueError(f"a bag of {n} rows got {c.numel()} cluster ids")
+        out.append(c.to(device))
+    c = out[0] if len(out) == 1 else torch.cat(out)          # ONE filter and cast for the chunk, not one per bag
+    ok = (c >= 0) & (c < Kc)
+    if c.is_floating_point():
+        ok &= c == c.floor()
+    return torch.where(ok, c, torch.full_like(c, -1)).to(torch.int32).contiguous()
+
+
+def cluster_pool_bags(bags, cluster_ids, Wp, bp, num_clusters: Optional[int] = None, ret_state: bool = False):
+    """DeepAttnMISL's ``phis`` + per-cluster mean over a chunk of 1..64 bags ([N_i, 512] bf16 or fp32 device rows, N_i >= 1, one dtype):
+    hc [B, Kc, 256] with hc[b, k] = mean over {n: cluster_ids[b][n] == k} of relu(Wp x_n + bp), zero for an empty cluster; ids outside
+    [0, Kc) belong to no cluster.  Wp: [256, 512] or the reference's [256, 512, 1, 1]; Kc = ``num_clusters`` (<= 16).  Differentiable
+    w.r.t. Wp and bp; a bag that requires grad raises (there is no dX).  The rows must be finite: a row of no cluster is kept out of hc
+    whatever it holds, but the backward multiplies every row by its (possibly zero) dpre.  ret_state: also (cnt [B, Kc] int32, mask [sum N_i, 8] int32:
+    bit j of a row's 256 set iff pre[j] > 0)."""
+    B = _chunk_len(bags)
+    _need_gpu(*bags)
+    _need_gpu(Wp, bp)
+    Kc = int(num_clusters if num_clusters is not None else 8)
+    if Wp.dim() not in (2, 4) or tuple(Wp.shape[:2]) != (256, 512) or Wp.numel() != 256 * 512 or bp.numel() != 256 or not (1 <= Kc <= 16):
+        raise VlsaNativeError(f"cluster_pool_bags: the HIP kernels cover dim_in = 512, dim_hid = 256, num_clusters <= 16 (got a weight of "
+                              f"{tuple(Wp.shape)}, {Kc} clusters); there is no other route")
+    if not isinstance(bags, BagSet):
+        bags = checked_bags(bags, 512, "cluster_pool_bags takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device",
+                            non_empty=True, no_grad="cluster_pool_bags: the bag requires grad, but the HIP backward produces the gradients "
+                                                    "of Wp and bp only (no dX)")
+    else:
+        _no_bag_grad(*bags)
+    plan = ClusterPoolPlan.of(bags)
+    ids = cluster_ids_int32(cluster_ids, plan.sizes, bags[0].device, Kc)
+    hc, cnt, mask = _ClusterPoolFn.apply(plan, ids, Kc, bool(ret_state), Wp, bp, *bags)
+    return (hc, cnt, mask) if ret_state else hc

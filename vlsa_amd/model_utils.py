@@ -16,7 +16,7 @@ from __future__ import annotations
 from typing import List, Optional
 
 __all__ = ["load_model", "Deep_VLSA", "get_prompt_encoder", "load_prompt_learner", "load_prompt_adapter", "patch_reference",
-           "arch_cfg_from_run_cfg", "func_load_model"]
+           "patch_reference_deepattnmisl", "unpatch_reference_deepattnmisl", "arch_cfg_from_run_cfg", "func_load_model"]
 
 
 _MISSING_DEPENDENCY = {"TransMIL": "nystrom_attention (NystromAttention)", "ILRA": "nystrom_attention (via model/deepmil.py's imports)",
@@ -29,7 +29,10 @@ def load_model(arch: str, dims: Optional[List] = None, **kws):
     with the reference's ``pooling`` assertions) and ``'DSMIL'`` (``vlsa_amd.deepmil.DSMIL``) -- from ``dims = [dim_in, dim_hid,
     num_cls]``.  DSMIL's backward reaches its own eight parameters, not the bag rows: with ``use_feat_proj=True`` (the constructor's
     default; every shipped cfg_sa_base_conch.yaml sets False) freeze ``model.feat_proj`` before training, or the first step raises.
-    TransMIL / ILRA / DeepAttnMISL / PatchGCN are not served: NotImplementedError names what they would need."""
+    TransMIL / ILRA / PatchGCN are not served, and DeepAttnMISL not THROUGH THIS FACTORY: NotImplementedError names what they would need.
+    DeepAttnMISL itself is served as ``vlsa_amd.deepmil.DeepAttnMISL`` (``forward(X, cluster_id)``, ``forward_bags(bags, cluster_ids)``:
+    phi + per-cluster mean in HIP); build it directly, or call ``patch_reference_deepattnmisl()`` and let the reference's own factory
+    and handler (which hands the model the cluster ids of its dataset pipeline) build and drive it."""
     if arch == "VLSA":
         return Deep_VLSA(**kws)
     if arch == "DeepMIL":
@@ -203,6 +206,35 @@ def patch_reference(resident_bags: bool = False, defer_training_calls: bool = Tr
                 if mod is not None and getattr(mod, "prepare_surv_dataset", None) is original:
                     mod.prepare_surv_dataset = prepare_surv_dataset
     return saved
+
+
+def patch_reference_deepattnmisl():
+    """Point the reference's DeepAttnMISL at this package's (separate from ``patch_reference``, which stays as it is):
+    ``model.deepmil.DeepAttnMISL`` and ``model.utils.DeepAttnMISL`` -- what ``load_model('DeepMIL', dims, network='DeepAttnMISL')``
+    (model/utils.py) builds -- and, if ``runner.sa_handler`` is loaded, the name its ``isinstance`` checks read.  Returns what it
+    replaced, for ``unpatch_reference_deepattnmisl``."""
+    import sys
+    import model.deepmil as ref_mil
+    import model.utils as ref_utils
+    from .deepmil import DeepAttnMISL
+    mods = [ref_mil, ref_utils]
+    handler = sys.modules.get("runner.sa_handler")
+    if handler is not None:
+        mods.append(handler)
+    saved = [(mod, getattr(mod, "DeepAttnMISL", _ABSENT)) for mod in mods]
+    for mod in mods:
+        mod.DeepAttnMISL = DeepAttnMISL
+    return saved
+
+
+def unpatch_reference_deepattnmisl(saved) -> None:
+    """Undo ``patch_reference_deepattnmisl`` (``saved`` = what it returned)."""
+    for mod, original in saved:
+        if original is _ABSENT:
+            if hasattr(mod, "DeepAttnMISL"):
+                delattr(mod, "DeepAttnMISL")
+        else:
+            mod.DeepAttnMISL = original
 
 
 def unpatch_reference(saved) -> None:
