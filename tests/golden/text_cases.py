@@ -12,6 +12,14 @@ TOWERS = {
     "small": dict(width=128, heads=2, layers=2, vocab=64, ctx=128, out_dim=64),
     "mid": dict(width=256, heads=4, layers=3, vocab=64, ctx=128, out_dim=128),
     "train": dict(width=128, heads=2, layers=2, vocab=64, ctx=128, out_dim=512),    # text features in the CONCH space [K, 512]
+    # tests/text_shape_cases.py: the sentence shapes the tower's kernels branch on.  Two blocks of the CONCH width take every CONCH
+    # specialisation at 1/6 of the weights; three give a block that is neither top nor bottom; 384 / 512 / 640 are the widths
+    # shape_of admits that no fixture has (runtime-G products, k_tt_ln_bwd / k_tt_ln_bwd4 with two slots)
+    "w768x2": dict(width=768, heads=12, layers=2, vocab=64, ctx=128, out_dim=512),
+    "w768x3": dict(width=768, heads=12, layers=3, vocab=64, ctx=128, out_dim=512),
+    "w384x2": dict(width=384, heads=6, layers=2, vocab=64, ctx=128, out_dim=128),
+    "w512x2": dict(width=512, heads=8, layers=2, vocab=64, ctx=128, out_dim=128),
+    "w640x2": dict(width=640, heads=10, layers=2, vocab=64, ctx=128, out_dim=128),
 }
 
 
@@ -19,7 +27,9 @@ TOWERS = {
 # random tower stay within |.| ~ 3 and the GELU inputs within ~ 2.5 -- a trained CONCH tower does not; the factors below drive the logits to
 # |.| ~ 30-60 (softmax rows close to one-hot, large exp arguments) and the c_fc outputs to |.| ~ 6-10 (GELU tails, erf saturating) -- ranges
 # the 1e-4 gate had never seen (VERDICT r5 "What's weak" 1).  seed -> (in_proj factor, c_fc factor).
-WEIGHT_SCALES = {9021: (3.5, 3.5), 9022: (4.0, 3.0), 9023: (3.0, 4.0)}
+WEIGHT_SCALES = {9021: (3.5, 3.5), 9022: (4.0, 3.0), 9023: (3.0, 4.0),
+                 # the weight seeds of tests/text_shape_cases.py (w768x2, w768x3, w384x2, w512x2, w640x2, small)
+                 9031: (3.5, 3.5), 9032: (3.5, 3.5), 9033: (3.5, 3.5), 9034: (3.5, 3.5), 9035: (3.5, 3.5), 9036: (3.5, 3.5)}
 
 
 def make_tower_weights(name: str, seed: int):

@@ -10,6 +10,7 @@ import torch.nn as nn
 import cases
 import text_cases as TC
 import text_helpers as TH
+from text_helpers import tower_kernels as _tower_kernels
 from test_text_modules_cpu import build_learner
 
 pytestmark = pytest.mark.gpu
@@ -92,6 +93,26 @@ def test_shared_prefix_of_many_prompts_takes_the_ticketed_fold():
     for a, b, what in zip(out["rows"], out["prefix"], ("features", "d context", "d rank")):
         err, scale = (a - b).abs().max().item(), max(1.0, a.abs().max().item())
         assert err < TOL * scale, (what, err, scale)
+    # ... and both against a third party: the CPU oracle in float64 over the full 128 positions (two routes that agree with each other
+    # could still share an error: the prefix block, the prompts' own rows and the scatter are common to them)
+    from oracle import text_oracle as TO
+    W = {k: v.double() for k, v in inp["W"].items()}
+    E = W["token_embedding.weight"]
+    bos, eos, pad = inp["special"]
+    ctx = pl.context_embeds.detach().cpu().double().requires_grad_(True)
+    rk = pl.rank_embeds.detach().cpu().double().requires_grad_(True)
+    pseudo = TO.pseudo_sentence_tokens(30, ctx.shape[0], rk.shape[1])
+    assert torch.equal(pseudo, tok.cpu())
+    template = TO.sentence_template(E[pad], E[bos], E[eos], E[inp["table"]["X."][1]], pseudo)
+    sent = TO.rank_prompt_learner_forward(ctx, rk, template, TO.interpolation_weights(case[4], 30).double(), 30, case[5])
+    assert (pl().detach().cpu().double() - sent.detach()).abs().max().item() < 1e-6
+    ref = TO.prompt_encoder_forward(W, inp["heads"], sent, pseudo, inp["layers"])
+    (ref * G.cpu().double()).sum().backward()
+    for name in ("rows", "prefix"):
+        for got, want, what in zip(out[name], (ref.detach(), ctx.grad, rk.grad), ("features", "d context", "d rank")):
+            err, scale = (got.cpu().double() - want).abs().max().item(), want.abs().max().item()
+            print(f"[ticketed fold, 30 prompts, {name}] {what}: {err:.2e} vs the float64 oracle (max|ref| {scale:.2e})")
+            assert err <= (TOL if what == "features" else TOL * scale + 1e-7), (name, what, err, scale)
 
 
 @pytest.mark.parametrize("case", TC.TEXT_CASES, ids=[c[0] for c in TC.TEXT_CASES])
@@ -341,15 +362,6 @@ def test_sentence_assembly_kernels_match_the_torch_ops(kind):
 
 
 # ---- the persistent forward (k_tt_forward_persistent): one launch for the 12 blocks, stages ordered by in-kernel counters --------
-def _tower_kernels(fn):
-    """names of the HIP kernels `fn` launches (torch profiler, device activity only)"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.key for e in prof.key_averages() for _ in range(e.count)]
-
-
 @pytest.mark.parametrize("name", ["rank_conch_k12", "rank_conch_k4", "text_conch"])
 def test_persistent_forward_equals_the_launch_per_stage_path(name, monkeypatch):
     """CONCH-size tower, <= 112 compact rows, VLSA_TT_PERSIST=1: the 12 blocks as ONE persistent launch (opt-in: measured slower than

@@ -50,3 +50,12 @@ def oracle_rank_case(case, requires_grad=False):
     sent = TO.rank_prompt_learner_forward(ctx, rk, template, interp, K, position)
     feats = TO.prompt_encoder_forward(W, inp["heads"], sent, pseudo, inp["layers"])
     return feats, dict(context=ctx, rank=rk, sentence=sent, pseudo=pseudo)
+
+
+def tower_kernels(fn):
+    """names of the HIP kernels `fn` launches (torch profiler, device activity only)"""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.key for e in prof.key_averages() for _ in range(e.count)]
