@@ -814,6 +814,52 @@ int vlsa_cluster_pool_backward_batch(const void* bag_desc, int B, int x_dtype, i
                                      const int64_t* row_off, const int* ids, const uint32_t* mask, const float* dhc, const int* cnt,
                                      void* ws, float* dWp, float* dbp, void* stream);
 
+/* ---- ILRA (model/deepmil.py:409-535, topk = 1, ln = False) over a table of bags: softmax pooling and the row map (csrc/ilra.hip) ------
+ * Common to the four entry points:
+ *   bag_desc   device table of B vlsa_bag_desc (1 <= B <= 64, one dtype).  The rows are EITHER the bags' own (xp == NULL: bf16 or fp32,
+ *              D == 512) OR the packed fp32 [sum N_b][256] output of a previous row map (xp != NULL, D == 256, x_dtype VLSA_DT_F32; the
+ *              table then supplies the bag sizes only).  Anything else: VLSA_EUNSUPPORTED.  Every product is the fp32-input MFMA; bf16
+ *              rows are widened exactly.
+ *   row_off    [B] int64 (device): first row of bag b among the launch's rows laid back to back (packed rows, outputs, mask).
+ *   part_start [B + 1] int32 (device): bag b owns vlsa_ilra_pool_parts(N_b) = clamp(ceil(N_b / vlsa_ilra_pool_part_rows()), 1, 64) partial
+ *              records (a function of N_b alone); n_parts =
+ *              part_start[B].  tile_start [B + 1] int32: first tile of bag b in tiles of vlsa_ilra_tile_rows() rows; n_tiles =
+ *              tile_start[B].  A bag's result is bit-equal alone and in a batch; all partial records are added in a fixed order.
+ *   VLSA_EINVAL: a NULL pointer, B outside [1, 64], a table shorter than B, P < 1, a dX asked for bag rows.  VLSA_EUNSUPPORTED: another
+ *              D, H != 256, P > 16, another dtype.
+ * vlsa_ilra_pool_forward_batch: Z[b][p][:] = sum_n softmax_n(E[p] . x_n) x_n for the P <= 16 queries E [P][D] shared by all bags (no row
+ *   norms, no scale); m, l [B][16]: the softmax's maximum and sum per (b, p), kept for the backward.  ws: vlsa_ilra_pool_workspace_bytes.
+ * vlsa_ilra_pool_backward_batch: with g = dZ [B][P][D], Z the forward's output and a_p(n) recomputed from m, l:
+ *   dE[p] = sum_b sum_n a_p(n) (g_p . x_n - g_p . z_p) x_n  [P][D], and for packed rows (dX non-NULL, [sum N_b][256], WRITTEN not added)
+ *   dX_n = sum_p a_p(n) (g_p + (g_p . x_n - g_p . z_p) e_p).  Both dot products run through the same chain: a one-row bag gives dE = 0.
+ * vlsa_ilra_rowmap_forward_batch: per row u = Wq x + btil[b], t = Wo u + bo, out = (u + relu(t)) * silu(Wg x + bg): out packed fp32
+ *   [sum N_b][256]; Wq, Wg [256][D], Wo [256][256], btil [B][256] (the layer's bias plus the bag's attention output).  mask (nullable)
+ *   [sum N_b][8] uint32: bit j of a row set iff t[j] > 0.
+ * vlsa_ilra_rowmap_backward_batch: dOut [sum N_b][256] -> dWq, dWg [256][D], dWo [256][256], dbtil [B][256], dbo, dbg [256] summed over
+ *   the launch's rows, the mask READ; for packed rows (dX non-NULL) dX = Wq^T du + Wg^T ds.  WoT [256][256], WqT, WgT [D][256] (needed
+ *   for dX only): the transposes, row-major.  total_rows = sum N_b.  ws: vlsa_ilra_rowmap_backward_workspace_bytes(total_rows, n_tiles,
+ *   B, D) = u, du, ds, dt staged as [total_rows][256] fp32 each, the row-split partials of one weight gradient (at most 64 splits) and
+ *   the column sums. */
+int vlsa_ilra_tile_rows(void);
+int vlsa_ilra_pool_part_rows(void);
+int vlsa_ilra_pool_parts(int64_t N);
+size_t vlsa_ilra_pool_workspace_bytes(int n_parts, int D);
+size_t vlsa_ilra_rowmap_backward_workspace_bytes(int64_t total_rows, int n_tiles, int B, int D);
+int vlsa_ilra_pool_forward_batch(const void* bag_desc, int B, int x_dtype, int D, int P, const int* part_start, int n_parts,
+                                 const int64_t* row_off, const void* xp, const float* E, void* ws, float* Z, float* m, float* l,
+                                 void* stream);
+int vlsa_ilra_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int P, const int* part_start, int n_parts,
+                                  const int64_t* row_off, const void* xp, const float* E, const float* dZ, const float* Z, const float* m,
+                                  const float* l, void* ws, float* dE, float* dX, void* stream);
+int vlsa_ilra_rowmap_forward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, const int* tile_start, int n_tiles,
+                                   const int64_t* row_off, const void* xp, const float* Wq, const float* btil, const float* Wo,
+                                   const float* bo, const float* Wg, const float* bg, float* out, uint32_t* mask, void* stream);
+int vlsa_ilra_rowmap_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, const int* tile_start, int n_tiles,
+                                    const int64_t* row_off, const void* xp, int64_t total_rows, const float* Wq, const float* btil,
+                                    const float* Wo, const float* bo, const float* Wg, const float* bg, const float* WoT, const float* WqT,
+                                    const float* WgT, const uint32_t* mask, const float* dOut, void* ws, float* dWq, float* dbtil,
+                                    float* dWo, float* dbo, float* dWg, float* dbg, float* dX, void* stream);
+
 /* Device-side descriptor tables of ONE bag for the *_backward entry points above (bag_desc [1], optional second table, row
  * offset [1], tile_start [2]) written from by-value arguments by a one-thread kernel: dst = 64 bytes of device memory.  Returns the
  * number of tiles (> 0) or a negative error code.  Layout: {X, N, ld} {extra, N, extra_ld}? {0} {int32 0, int32 n_tiles}. */

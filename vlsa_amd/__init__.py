@@ -5,11 +5,14 @@ in hand-written HIP kernels behind the C ABI of include/vlsa_hip.h.  There is no
 """
 from ._native import VlsaNativeError  # noqa: F401
 
-__all__ = ["VlsaNativeError", "DeepAttnMISL"]
+__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA"]
 
 
 def __getattr__(name):
     if name == "DeepAttnMISL":          # imported on first use: the package itself needs no torch
         from .deepmil import DeepAttnMISL
         return DeepAttnMISL
+    if name == "ILRA":
+        from .deepmil import ILRA
+        return ILRA
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

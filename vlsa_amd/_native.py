@@ -203,6 +203,16 @@ _SIGNATURES = {
     "vlsa_cluster_pool_backward_workspace_bytes": (c_size_t, [c_int]),
     "vlsa_cluster_pool_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
     "vlsa_cluster_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
+    "vlsa_ilra_tile_rows": (c_int, []),
+    "vlsa_ilra_pool_part_rows": (c_int, []),
+    "vlsa_ilra_pool_parts": (c_int, [c_int64]),
+    "vlsa_ilra_pool_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vlsa_ilra_rowmap_backward_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "vlsa_ilra_pool_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 8),
+    "vlsa_ilra_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 11),
+    "vlsa_ilra_rowmap_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 11),
+    "vlsa_ilra_rowmap_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64]
+                                        + [c_void_p] * 20),
     "vlsa_debug_probe": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),
     "vlsa_xchg_max_peers": (c_int, []),
     "vlsa_xchg_result_floats": (c_size_t, [c_int, c_int, c_int, c_void_p]),

@@ -718,3 +718,179 @@ class DeepAttnMISL(nn.Module):
 
     def forward(self, X, cluster_id, *args):
         return self.forward_bags([X], [cluster_id])
+
+
+# ---- ILRA (Xiang et al., ICLR 2023; model/deepmil.py:409-535) ---------------------------------------------------------------------
+def _ilra_initialize_weights(model):
+    """model/deepmil.py:409-417"""
+    for m in model.modules():
+        if isinstance(m, nn.Linear):
+            nn.init.xavier_normal_(m.weight)
+        elif isinstance(m, nn.BatchNorm1d):
+            nn.init.constant_(m.weight, 1)
+            nn.init.constant_(m.bias, 0)
+
+
+class _IlraMHA(nn.Module):
+    """The parameters of the reference's ``MultiHeadAttention`` block (model/deepmil.py:420-452) under its own names; it is never
+    called: ``ILRA.forward_bags`` reads the parameters and drives the kernels."""
+
+    def __init__(self, dim_Q, dim_K, dim_V, num_heads, ln=False, gated=False):
+        super().__init__()
+        self.dim_V, self.num_heads = dim_V, num_heads
+        self.multihead_attn = nn.MultiheadAttention(dim_V, num_heads)
+        self.fc_q = nn.Linear(dim_Q, dim_V)
+        self.fc_k = nn.Linear(dim_K, dim_V)
+        self.fc_v = nn.Linear(dim_K, dim_V)
+        if ln:
+            self.ln0 = nn.LayerNorm(dim_V)
+            self.ln1 = nn.LayerNorm(dim_V)
+        self.fc_o = nn.Linear(dim_V, dim_V)
+        self.gate = None
+        if gated:
+            self.gate = nn.Sequential(nn.Linear(dim_Q, dim_V), nn.SiLU())
+
+
+class _IlraGAB(nn.Module):
+    def __init__(self, dim_in, dim_out, num_heads, num_inds, ln=False):
+        super().__init__()
+        self.latent = nn.Parameter(torch.Tensor(1, num_inds, dim_out))
+        nn.init.xavier_uniform_(self.latent)
+        self.project_forward = _IlraMHA(dim_out, dim_in, dim_out, num_heads, ln=ln, gated=True)
+        self.project_backward = _IlraMHA(dim_in, dim_out, dim_out, num_heads, ln=ln, gated=True)
+
+
+class _IlraNLP(nn.Module):
+    def __init__(self, dim, num_heads, num_seeds, ln=False):
+        super().__init__()
+        self.S = nn.Parameter(torch.Tensor(1, num_seeds, dim))
+        nn.init.xavier_uniform_(self.S)
+        self.mha = _IlraMHA(dim, dim, dim, num_heads, ln=ln)
+
+
+def _d(t):
+    return t.double()
+
+
+class ILRA(nn.Module):
+    """ILRA with the reference's constructor, initialisation and state-dict keys (``gab_blocks.{i}.latent``,
+    ``gab_blocks.{i}.project_{forward,backward}.*``, ``pooling.S``, ``pooling.mha.*``, ``classifier.*``); the modules hold parameters
+    only.  For ``topk = 1`` the model is, per block, ONE softmax pooling of the rows against eight effective queries (one latent, eight
+    heads: ``E_h = (Wik_h Wk)^T q'_h / sqrt(32)`` -- parameters only, computed once per call), a [1, 256]-sized tail, and one row map
+    (``project_backward`` has a single key, so every row gets the same attention output c: ``u = Wq x + bq + c``, ``xhat = (u +
+    relu(Wo u + bo)) * silu(Wg x + bg)``); then the same pooling over the last block's rows and the classifier.  The two N-sized
+    operations are HIP (csrc/ilra.hip), forward and backward; the tails are torch ops on [B, 8, d] / [B, 256] tensors EVALUATED IN
+    FLOAT64 (fp32 parameters cast in the graph, autocast switched off), so every parameter gets its gradient through ordinary autograd.
+    ``fc_k`` and the q / k thirds of ``in_proj`` of ``project_backward`` get exact zeros, as the reference's autograd gives.
+
+    Served: ``dim_in = 512``, ``dim_hid = 256``, ``num_heads = 8``, ``topk = 1``, ``ln = False``, ``num_layers >= 1``, any ``num_cls``;
+    anything else constructs (checkpoints load) and raises ``VlsaNativeError`` from ``forward``.  Bags are bf16 or fp32 device rows without
+    a gradient of their own.  There is no dropout: ``train()`` and ``eval()`` compute the same."""
+
+    ROW_BUDGET = 1 << 20          # rows per chunk of forward_bags (a bigger bag travels alone): bounds the packed activations
+
+    def __init__(self, dim_in=512, dim_hid=256, num_cls=2, num_layers=2, num_heads=8, topk=1, ln=False, **kwargs):
+        super().__init__()
+        self.cfg = dict(dim_in=dim_in, dim_hid=dim_hid, num_layers=num_layers, num_heads=num_heads, topk=topk, ln=ln)
+        self.gab_blocks = nn.ModuleList([_IlraGAB(dim_in=dim_in if i == 0 else dim_hid, dim_out=dim_hid, num_heads=num_heads, num_inds=topk,
+                                                  ln=ln) for i in range(num_layers)])
+        self.pooling = _IlraNLP(dim=dim_hid, num_heads=num_heads, num_seeds=topk, ln=ln)
+        self.classifier = nn.Linear(in_features=dim_hid, out_features=num_cls)
+        _ilra_initialize_weights(self)
+        print("[setup] initialized an ILRA model.")
+
+    def _check_served(self):
+        c = self.cfg
+        if (c["dim_in"], c["dim_hid"], c["num_heads"], c["topk"], bool(c["ln"])) != (512, 256, 8, 1, False) or c["num_layers"] < 1:
+            raise VF.VlsaNativeError(f"ILRA: the HIP kernels cover dim_in = 512, dim_hid = 256, num_heads = 8, topk = 1, ln = False, "
+                                     f"num_layers >= 1 (got {c}); there is no other route")
+
+    @staticmethod
+    def _queries(mha, seed):
+        """(fc_q(seed) [256], E [8, d]) of an attention block whose query is the one row ``seed`` [1, 1, 256], in float64"""
+        a = mha.multihead_attn
+        Wi, bi = _d(a.in_proj_weight), _d(a.in_proj_bias)
+        qf = F.linear(_d(seed).view(1, 256), _d(mha.fc_q.weight), _d(mha.fc_q.bias))[0]              # the "Q" of O = Q + A
+        qf = qf + 0.0 * _d(mha.fc_k.bias).sum()          # the key biases are constant over the rows and cancel in the softmax: exact zeros
+        qp = F.linear(qf, Wi[:256], bi[:256])
+        M = Wi[256:512] @ _d(mha.fc_k.weight)                                                           # [256, d]
+        E = (qp.view(8, 32, 1) * M.view(8, 32, -1)).sum(1) / math.sqrt(32.0)
+        return qf, E
+
+    @staticmethod
+    def _tail(mha, qf, Z, seed):
+        """[B, 256] behind the pooling Z [B, 8, d] (float64): values, per-head pick, out_proj, residual, fc_o, gate"""
+        a = mha.multihead_attn
+        Wi, bi = _d(a.in_proj_weight), _d(a.in_proj_bias)
+        v = F.linear(F.linear(Z, _d(mha.fc_v.weight), _d(mha.fc_v.bias)), Wi[512:], bi[512:])           # [B, 8, 256]
+        B = v.shape[0]
+        A = v.view(B, 8, 8, 32).diagonal(dim1=1, dim2=2).permute(0, 2, 1).reshape(B, 256)             # head h's 32 entries of row h
+        O = qf[None, :] + F.linear(A, _d(a.out_proj.weight), _d(a.out_proj.bias))
+        O = O + torch.relu(F.linear(O, _d(mha.fc_o.weight), _d(mha.fc_o.bias)))
+        if mha.gate is not None:
+            g = mha.gate._modules["0"]
+            O = O * F.silu(F.linear(_d(seed).view(1, 256), _d(g.weight), _d(g.bias)))
+        return O
+
+    def _chunk(self, bags, prep, ret_state):
+        """logits [B, num_cls] of one chunk of <= 64 bags; prep: the per-call (qf, E) of every block and of the pooling"""
+        xp, state = None, {}
+        for i, blk in enumerate(self.gab_blocks):
+            pf, pb = blk.project_forward, blk.project_backward
+            qf, E = prep[i]
+            Z = VF.ilra_pool_bags(bags, E.float(), xp)
+            H = self._tail(pf, qf, Z.double(), blk.latent)
+            a = pb.multihead_attn
+            c = F.linear(F.linear(F.linear(H, _d(pb.fc_v.weight), _d(pb.fc_v.bias)), _d(a.in_proj_weight)[512:], _d(a.in_proj_bias)[512:]),
+                         _d(a.out_proj.weight), _d(a.out_proj.bias))
+            # fc_k of project_backward feeds a softmax over ONE key: it joins the graph with weight 0, so that it receives the exact zeros
+            # the reference's autograd gives (an optimizer with weight decay treats a missing gradient and a zero one differently)
+            c = c + 0.0 * (_d(pb.fc_k.weight).sum() + _d(pb.fc_k.bias).sum())
+            btil = (_d(pb.fc_q.bias)[None, :] + c).float()
+            g = pb.gate._modules["0"]
+            out = VF.ilra_rowmap_bags(bags, pb.fc_q.weight, btil, pb.fc_o.weight, pb.fc_o.bias, g.weight, g.bias, xp, ret_mask=ret_state)
+            xp, mask = out if ret_state else (out, None)
+            if ret_state:
+                state[f"Z{i}"], state[f"H{i}"], state[f"mask{i}"], state[f"xhat{i}"] = Z, H, mask, xp
+        qf, E = prep[-1]
+        Z = VF.ilra_pool_bags(bags, E.float(), xp)
+        feat = self._tail(self.pooling.mha, qf, Z.double(), self.pooling.S)
+        logits = F.linear(feat, _d(self.classifier.weight), _d(self.classifier.bias)).float()
+        if ret_state:
+            state["Zp"], state["feat"] = Z, feat
+        return logits, state
+
+    def forward_bags(self, bags, ret_state=False):
+        """logits [B, num_cls] of a list of bags ([N_i, 512] or [1, N_i, 512], bf16 or fp32 device rows) or a ``BagSet``:
+        ``torch.cat([self(x) for x in bags])``, in chunks of <= 64 bags and <= ROW_BUDGET rows per launch chain.  A ``BagSet`` is taken
+        as it is (no per-bag checks, no host synchronisation, no staging upload once its descriptor table is up).  ret_state: also a
+        list of per-chunk dicts (Z{i}, H{i}, mask{i}, xhat{i} per block, Zp, feat)."""
+        self._check_served()
+        if len(bags) == 0:
+            raise ValueError("forward_bags needs at least one bag")
+        if isinstance(bags, VF.BagSet):
+            sizes = bags.sizes
+        else:
+            bags = VF.checked_bags(bags, 512, "ILRA takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device",
+                                   non_empty=True, no_grad="ILRA: the bag requires grad, but bag rows receive no gradient from the HIP kernels")
+            sizes = [int(x.shape[0]) for x in bags]
+        VF._need_gpu(self.classifier.weight)
+        with torch.autocast(device_type="cuda", enabled=False):
+            prep = [self._queries(blk.project_forward, blk.latent) for blk in self.gab_blocks]
+            prep.append(self._queries(self.pooling.mha, self.pooling.S))
+            outs, states, i = [], [], 0
+            while i < len(sizes):
+                j, rows = i + 1, sizes[i]
+                while j < len(sizes) and j - i < 64 and rows + sizes[j] <= self.ROW_BUDGET:
+                    rows += sizes[j]
+                    j += 1
+                chunk = bags.chunk(i, j - i) if isinstance(bags, VF.BagSet) else bags[i:j]
+                lg, st = self._chunk(chunk, prep, ret_state)
+                outs.append(lg)
+                states.append(st)
+                i = j
+        logits = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return (logits, states) if ret_state else logits
+
+    def forward(self, X):
+        return self.forward_bags([X])

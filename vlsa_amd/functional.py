@@ -2133,3 +2133,150 @@ def cluster_pool_bags(bags, cluster_ids, Wp, bp, num_clusters: Optional[int] = N
     ids = cluster_ids_int32(cluster_ids, plan.sizes, bags[0].device, Kc)
     hc, cnt, mask = _ClusterPoolFn.apply(plan, ids, Kc, bool(ret_state), Wp, bp, *bags)
     return (hc, cnt, mask) if ret_state else hc
+
+
+# ---- ILRA (model/deepmil.py:409-535, topk = 1): softmax pooling and the row map over a table of bags --------------------------------
+class IlraPlan(_ChunkPlan):
+    """Device tables of one chunk of <= 64 bags for the vlsa_ilra_* entry points: the descriptor table, the row offsets, part_start
+    [B + 1] (bag b owns vlsa_ilra_pool_parts(N_b) partial records -- a function of N_b alone) and tile_start for the row map's tiles.
+    Derived from the descriptor table by in-stream ops on the device (a ``BagSet``'s table is already there; a plain list's is staged
+    from the host first); the tile, the rows per part and the cap on the parts are asked of the library."""
+
+    def __init__(self, bags):
+        lib = nat.load()
+        super().__init__(_chunk_tables(bags, "the batched ILRA route over a plain list of bags"))
+        self.n_parts = sum(int(lib.vlsa_ilra_pool_parts(n)) for n in self.sizes)
+        rows, cap = int(lib.vlsa_ilra_pool_part_rows()), int(lib.vlsa_ilra_pool_parts(1 << 62))
+        n = self.desc[:, 1]
+        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
+        self.part_start[1:] = torch.cumsum(torch.clamp(torch.div(n + (rows - 1), rows, rounding_mode="floor"), 1, cap), 0)
+        self.ts, self.n_tiles = self.tables.tile_start(int(lib.vlsa_ilra_tile_rows()))
+
+
+class _IlraPoolFn(torch.autograd.Function):
+    """Z [B, P, D] = softmax_n(E[p] . x_n) x_n over a chunk of <= 64 bags as ONE autograd node (two launches forward, two backward).
+    ``xp``: None = the bags' own rows (D = 512, no gradient), else the packed fp32 [sum N_i, 256] rows of a previous row map, which
+    receive a gradient.  Gradients for E and xp."""
+
+    @staticmethod
+    def forward(ctx, plan, xp, E, *bag_tensors):
+        lib, s = nat.load(), _stream()
+        dev, B = plan.desc.device, plan.B
+        Ef = _f32c(E)
+        P, D = Ef.shape
+        xpf = None if xp is None else _f32c(xp)
+        ws = torch.empty(lib.vlsa_ilra_pool_workspace_bytes(plan.n_parts, D), dtype=torch.uint8, device=dev)
+        Z = torch.empty(B, P, D, dtype=torch.float32, device=dev)
+        m = torch.empty(B, 16, dtype=torch.float32, device=dev)
+        l = torch.empty(B, 16, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_ilra_pool_forward_batch(_p(plan.desc), B, nat.DT_F32 if xp is not None else plan.dt, D, P, _p(plan.part_start),
+                                                   plan.n_parts, _p(plan.a_off), _p(xpf), _p(Ef), _p(ws), _p(Z), _p(m), _p(l), s),
+                  "vlsa_ilra_pool_forward_batch")
+        ctx.save_for_backward(Ef, Z, m, l, xpf)
+        ctx.plan, ctx.bags = plan, bag_tensors        # the kernels read the bags through the descriptor table
+        return Z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dZ):
+        lib, s = nat.load(), _stream()
+        Ef, Z, m, l, xpf = ctx.saved_tensors
+        plan = ctx.plan
+        dev, B = Z.device, plan.B
+        P, D = Ef.shape
+        g = _f32c(dZ)
+        ws = torch.empty(lib.vlsa_ilra_pool_workspace_bytes(plan.n_parts, D), dtype=torch.uint8, device=dev)
+        dE = torch.empty(P, D, dtype=torch.float32, device=dev)
+        dX = torch.empty_like(xpf) if (xpf is not None and ctx.needs_input_grad[1]) else None
+        nat.check(lib.vlsa_ilra_pool_backward_batch(_p(plan.desc), B, nat.DT_F32 if xpf is not None else plan.dt, D, P, _p(plan.part_start),
+                                                    plan.n_parts, _p(plan.a_off), _p(xpf), _p(Ef), _p(g), _p(Z), _p(m), _p(l), _p(ws), _p(dE),
+                                                    _p(dX), s), "vlsa_ilra_pool_backward_batch")
+        return (None, dX, dE, *([None] * len(ctx.bags)))
+
+
+class _IlraRowMapFn(torch.autograd.Function):
+    """xhat [sum N_i, 256] = (u + relu(Wo u + bo)) * silu(Wg x + bg), u = Wq x + btil[b], over a chunk of <= 64 bags as ONE autograd
+    node.  The forward keeps the ReLU decisions (256 bits per row); the backward reads them.  Gradients for the six parameters and, for
+    packed rows (``xp``), the rows."""
+
+    @staticmethod
+    def forward(ctx, plan, xp, want_mask, Wq, btil, Wo, bo, Wg, bg, *bag_tensors):
+        lib, s = nat.load(), _stream()
+        dev, B = plan.desc.device, plan.B
+        w = [_f32c(t) for t in (Wq, btil, Wo, bo, Wg, bg)]
+        D = w[0].shape[1]
+        xpf = None if xp is None else _f32c(xp)
+        out = torch.empty(plan.total, 256, dtype=torch.float32, device=dev)
+        keep = want_mask or any(ctx.needs_input_grad[1:9])
+        mask = torch.empty(plan.total, 8, dtype=torch.int32, device=dev) if keep else None
+        nat.check(lib.vlsa_ilra_rowmap_forward_batch(_p(plan.desc), B, nat.DT_F32 if xp is not None else plan.dt, D, w[0].shape[0], _p(plan.ts),
+                                                     plan.n_tiles, _p(plan.a_off), _p(xpf), *[_p(t) for t in w], _p(out), _p(mask), s),
+                  "vlsa_ilra_rowmap_forward_batch")
+        ctx.save_for_backward(*w, mask, xpf)
+        ctx.plan, ctx.bags = plan, bag_tensors
+        ctx.shapes = [t.shape for t in (Wq, btil, Wo, bo, Wg, bg)]
+        if mask is None:
+            mask = torch.empty(0, 8, dtype=torch.int32, device=dev)
+        ctx.mark_non_differentiable(mask)
+        return out, mask
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dmask):
+        lib, s = nat.load(), _stream()
+        Wq, btil, Wo, bo, Wg, bg, mask, xpf = ctx.saved_tensors
+        plan = ctx.plan
+        dev, B, D = Wq.device, plan.B, Wq.shape[1]
+        g = _f32c(dout)
+        want_dx = xpf is not None and ctx.needs_input_grad[1]
+        WoT = Wo.t().contiguous()
+        WqT, WgT = (Wq.t().contiguous(), Wg.t().contiguous()) if want_dx else (None, None)
+        ws = torch.empty(lib.vlsa_ilra_rowmap_backward_workspace_bytes(plan.total, plan.n_tiles, B, D), dtype=torch.uint8, device=dev)
+        grads = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes]
+        dX = torch.empty_like(xpf) if want_dx else None
+        nat.check(lib.vlsa_ilra_rowmap_backward_batch(_p(plan.desc), B, nat.DT_F32 if xpf is not None else plan.dt, D, 256, _p(plan.ts),
+                                                      plan.n_tiles, _p(plan.a_off), _p(xpf), plan.total, _p(Wq), _p(btil), _p(Wo), _p(bo),
+                                                      _p(Wg), _p(bg), _p(WoT), _p(WqT), _p(WgT), _p(mask), _p(g), _p(ws), *[_p(t) for t in grads],
+                                                      _p(dX), s), "vlsa_ilra_rowmap_backward_batch")
+        return (None, dX, None, *grads, *([None] * len(ctx.bags)))
+
+
+def _ilra_rows(bags, xp, what):
+    """the validated chunk (a ``BagSet`` as it is) and its plan; ``xp``: packed fp32 [sum N_i, 256] rows that replace the bags' own"""
+    _chunk_len(bags)
+    if not isinstance(bags, BagSet):
+        bags = checked_bags(bags, 512, f"{what} takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device", non_empty=True,
+                            no_grad=f"{what}: the bag requires grad, but bag rows receive no gradient from the HIP kernels")
+    else:
+        _no_bag_grad(*bags)
+    plan = IlraPlan.of(bags)
+    if xp is not None and (not xp.is_cuda or xp.dim() != 2 or tuple(xp.shape) != (plan.total, 256)):
+        raise VlsaNativeError(f"{what}: packed rows must be a device [sum N_i, 256] tensor (got {tuple(xp.shape)} for {plan.total} rows)")
+    return bags, plan
+
+
+def ilra_pool_bags(bags, E, xp=None):
+    """Z [B, P, D] with Z[b, p] = sum_n softmax_n(E[p] . x_n) x_n over a chunk of 1..64 bags ([N_i, 512] bf16 or fp32 device rows) for
+    P <= 16 queries E [P, D] shared by the bags; with ``xp`` (fp32 [sum N_i, 256], the output of ``ilra_rowmap_bags`` on the same bags)
+    the rows are xp's and D = 256.  Differentiable w.r.t. E and xp; a bag that requires grad raises."""
+    _need_gpu(E, *bags)
+    D = 512 if xp is None else 256
+    if E.dim() != 2 or E.shape[1] != D or not (1 <= E.shape[0] <= 16):
+        raise VlsaNativeError(f"ilra_pool_bags: the HIP kernels cover 1..16 queries of width {D} (got {tuple(E.shape)}); there is no other route")
+    bags, plan = _ilra_rows(bags, xp, "ilra_pool_bags")
+    return _IlraPoolFn.apply(plan, xp, E, *bags)
+
+
+def ilra_rowmap_bags(bags, Wq, btil, Wo, bo, Wg, bg, xp=None, ret_mask: bool = False):
+    """ILRA's ``project_backward`` per row over a chunk of 1..64 bags: xhat fp32 [sum N_i, 256] = (u + relu(Wo u + bo)) * silu(Wg x + bg)
+    with u = Wq x + btil[b]; Wq, Wg [256, D], Wo [256, 256], btil [B, 256].  Rows as in ``ilra_pool_bags``.  Differentiable w.r.t. the six
+    parameters and xp.  ret_mask: also the ReLU decisions [sum N_i, 8] int32 (bit j of a row's 256 set iff t[j] > 0)."""
+    _need_gpu(Wq, btil, Wo, bo, Wg, bg, *bags)
+    D = 512 if xp is None else 256
+    if (tuple(Wq.shape) != (256, D) or tuple(Wg.shape) != (256, D) or tuple(Wo.shape) != (256, 256) or bo.numel() != 256 or bg.numel() != 256
+            or tuple(btil.shape) != (len(bags), 256)):
+        raise VlsaNativeError(f"ilra_rowmap_bags: the HIP kernels cover dim_hid = 256 on {D} features and one bias row per bag (got Wq "
+                              f"{tuple(Wq.shape)}, Wo {tuple(Wo.shape)}, Wg {tuple(Wg.shape)}, btil {tuple(btil.shape)}); there is no other route")
+    bags, plan = _ilra_rows(bags, xp, "ilra_rowmap_bags")
+    out, mask = _IlraRowMapFn.apply(plan, xp, bool(ret_mask), Wq, btil, Wo, bo, Wg, bg, *bags)
+    return (out, mask) if ret_mask else out

@@ -16,7 +16,7 @@ from __future__ import annotations
 from typing import List, Optional
 
 __all__ = ["load_model", "Deep_VLSA", "get_prompt_encoder", "load_prompt_learner", "load_prompt_adapter", "patch_reference",
-           "patch_reference_deepattnmisl", "unpatch_reference_deepattnmisl", "arch_cfg_from_run_cfg", "func_load_model"]
+           "patch_reference_deepattnmisl", "unpatch_reference_deepattnmisl", "patch_reference_ilra", "unpatch_reference_ilra", "arch_cfg_from_run_cfg", "func_load_model"]
 
 
 _MISSING_DEPENDENCY = {"TransMIL": "nystrom_attention (NystromAttention)", "ILRA": "nystrom_attention (via model/deepmil.py's imports)",
@@ -29,7 +29,9 @@ def load_model(arch: str, dims: Optional[List] = None, **kws):
     with the reference's ``pooling`` assertions) and ``'DSMIL'`` (``vlsa_amd.deepmil.DSMIL``) -- from ``dims = [dim_in, dim_hid,
     num_cls]``.  DSMIL's backward reaches its own eight parameters, not the bag rows: with ``use_feat_proj=True`` (the constructor's
     default; every shipped cfg_sa_base_conch.yaml sets False) freeze ``model.feat_proj`` before training, or the first step raises.
-    TransMIL / ILRA / PatchGCN are not served, and DeepAttnMISL not THROUGH THIS FACTORY: NotImplementedError names what they would need.
+    TransMIL / PatchGCN are not served, and DeepAttnMISL / ILRA not THROUGH THIS FACTORY: NotImplementedError names what they would need.
+    ILRA is served as ``vlsa_amd.deepmil.ILRA`` (``forward(X)``, ``forward_bags(bags)``: softmax pooling and the row map in HIP, forward
+    and backward); build it directly, or call ``patch_reference_ilra()`` and let the reference's own factory build it.
     DeepAttnMISL itself is served as ``vlsa_amd.deepmil.DeepAttnMISL`` (``forward(X, cluster_id)``, ``forward_bags(bags, cluster_ids)``:
     phi + per-cluster mean in HIP); build it directly, or call ``patch_reference_deepattnmisl()`` and let the reference's own factory
     and handler (which hands the model the cluster ids of its dataset pipeline) build and drive it."""
@@ -235,6 +237,34 @@ def unpatch_reference_deepattnmisl(saved) -> None:
                 delattr(mod, "DeepAttnMISL")
         else:
             mod.DeepAttnMISL = original
+
+
+def patch_reference_ilra():
+    """Point the reference's ILRA at this package's (separate from ``patch_reference``, which stays as it is): ``model.deepmil.ILRA`` and
+    ``model.utils.ILRA`` -- what ``load_model('DeepMIL', dims, network='ILRA')`` (model/utils.py) builds -- and, if ``runner.sa_handler``
+    is loaded and carries the name, that one too.  Returns what it replaced, for ``unpatch_reference_ilra``."""
+    import sys
+    import model.deepmil as ref_mil
+    import model.utils as ref_utils
+    from .deepmil import ILRA
+    mods = [ref_mil, ref_utils]
+    handler = sys.modules.get("runner.sa_handler")
+    if handler is not None and hasattr(handler, "ILRA"):
+        mods.append(handler)
+    saved = [(mod, getattr(mod, "ILRA", _ABSENT)) for mod in mods]
+    for mod in mods:
+        mod.ILRA = ILRA
+    return saved
+
+
+def unpatch_reference_ilra(saved) -> None:
+    """Undo ``patch_reference_ilra`` (``saved`` = what it returned)."""
+    for mod, original in saved:
+        if original is _ABSENT:
+            if hasattr(mod, "ILRA"):
+                delattr(mod, "ILRA")
+        else:
+            mod.ILRA = original
 
 
 def unpatch_reference(saved) -> None:
