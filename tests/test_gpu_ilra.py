@@ -18,21 +18,10 @@ TOL = IH.TOL
 
 
 def _bag(x, rows):
-    t = torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-    return (t.bfloat16() if rows == "bf16" else t).contiguous()
+    return IH.bag(x, rows, DEV)
 
 
-def _rel(tag, got, want, natural=None):
-    """within TOL of the largest float64 entry.  natural: the size the terms of the sum have; where the exact result is identically zero
-    (one row: the softmax is 1 and dE vanishes) or rounding noise against it, a relative error does not exist and ``natural`` is the
-    scale -- the ``grad_scale`` rule of ilra_helpers.py"""
-    want = np.asarray(want, dtype=np.float64)
-    scale = float(np.abs(want).max())
-    if natural is not None and scale <= 1e-9 * natural:
-        scale = natural
-    e = float(np.abs(got.detach().double().cpu().numpy() - want).max() / max(scale, 1e-30))
-    print(f"[ilra {tag}] rel err {e:.2e} (gate {TOL:.0e}, scale {scale:.2e})")
-    assert e <= TOL, (tag, e)
+_rel = IH.rel          # within TOL of the largest float64 entry, with the ``natural`` rule (ilra_helpers.py)
 
 
 # ---- the entry points alone --------------------------------------------------------------------------------------------------------
@@ -41,12 +30,7 @@ SOURCES = [("bf16", 512), ("f32", 512), ("act", 256)]
 
 
 def _source(N, src, seed):
-    """(bags, xp or None, float64 rows [N, D])"""
-    x = IC.make_bag(N, "bf16" if src != "f32" else "f32", seed)
-    if src != "act":
-        return [_bag(x, src)], None, torch.from_numpy(x).double()
-    a = (np.random.RandomState(seed + 7).standard_normal((N, 256)) * 0.4).astype(np.float32)
-    return [_bag(x, "bf16")], torch.from_numpy(a).to(DEV), torch.from_numpy(a).double()
+    return IH.source(N, src, seed, DEV)
 
 
 @pytest.mark.parametrize("src,D", SOURCES)
@@ -80,10 +64,7 @@ def test_row_map_alone(N, src, D):
     from vlsa_amd import functional as VF
     rs = np.random.RandomState(500 + N)
     bags, xp, X = _source(N, src, 350 + N)
-    names = ("Wq", "btil", "Wo", "bo", "Wg", "bg")
-    shp = ((256, D), (1, 256), (256, 256), (256,), (256, D), (256,))
-    sc = (2 * np.sqrt(2 / (256 + D)), 0.3, 2 * np.sqrt(1 / 256), 0.05, 2 * np.sqrt(2 / (256 + D)), 0.05)
-    P = {k: torch.from_numpy((rs.standard_normal(s) * c).astype(np.float32)) for k, s, c in zip(names, shp, sc)}
+    names, P = IH.ROWMAP_KEYS, IH.rowmap_params(rs, D)
     G = torch.from_numpy(rs.standard_normal((N, 256)).astype(np.float32))
     Pg = {k: v.to(DEV).requires_grad_(True) for k, v in P.items()}
     if xp is not None:
