@@ -754,8 +754,8 @@ int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc, int B, int
  * u_k = Wq^T qmax_k / sqrt(H) weights the un-normalised rows; B = Wv z + bv, logits = 0.5 (fcc(B) + cmax).  All products are fp32 FMA.
  *   bag_desc   device table of B vlsa_bag_desc (1 <= B <= 64, bf16 or fp32 rows, one dtype).  D == 512, H == 256, 1 <= C <= 16:
  *              VLSA_EUNSUPPORTED otherwise.
- *   part_start [B + 1] int32 (device): bag b owns the partial records part_start[b] .. part_start[b + 1], vlsa_dsmil_parts(N_b) of
- *              them -- a function of N_b alone, so a bag's result does not depend on the batch it travels in; n_parts = part_start[B].
+ *   part_start [B + 1] int32 (device): bag b owns the partial records part_start[b] .. part_start[b + 1], vlsa_dsmil_parts(N_b) =
+ *              clamp(ceil(N_b / vlsa_dsmil_part_rows()), 1, 64) of them -- a function of N_b alone, so a bag's result does not depend on the batch it travels in; n_parts = part_start[B].
  *   Wc [C][512], bc [C]  i_classifier.fc.0;  Wq [256][512], bq [256]  b_classifier.q;  Wv, bv  b_classifier.v.1;
  *   Wf [C][C][256], bf [C]  b_classifier.fcc (Conv1d(C, C, kernel_size = 256)).
  *   drop_p     b_classifier.v.0 in training mode: the value side sees x_n[f] * keep(seed_b, n, f) / (1 - drop_p) with the counter-
@@ -769,6 +769,7 @@ int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc, int B, int
  * vlsa_dsmil_backward_batch: the parameter gradients of sum_b dlogits[b] . logits[b], summed over the bags in bag order
  * (bit-reproducible): one streaming pass that recomputes A from (m2, l) and regenerates the masks, and three small launches.  The bag
  * rows receive no gradient.  Same drop_p / seed_word contents as the forward it belongs to. */
+int vlsa_dsmil_part_rows(void);
 int vlsa_dsmil_parts(int64_t N);
 size_t vlsa_dsmil_workspace_bytes(int n_parts, int C);
 size_t vlsa_dsmil_state_floats(int B, int C, int64_t* offsets9);

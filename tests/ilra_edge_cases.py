@@ -69,7 +69,7 @@ for src in ("bf16", "f32"):
     for N in (17, 300):
         for kind in ("pool", "rowmap"):
             _add("strided", kind, (N,), src, stride=1024)
-# ---- ragged tables for every source: find_bag past bag 0, row offsets, a second b~ row, wgrad splits across bags --- yardstick 3.6e-6
+# ---- ragged tables for every source: the bag lookup past bag 0, row offsets, a second b~ row, wgrad splits across bags --- yardstick 3.6e-6
 # f32: 19 row-map tiles in 5 splits, split 0 walks the tiles 0, 5, 10, 15 = bags 0, 1, 3, 3
 RAGGED = {"bf16": (33, 1, 300), "f32": (17, 130, 1, 300, 64), "act": (40, 257, 7, 33)}
 for src, sizes in RAGGED.items():

@@ -159,11 +159,18 @@ def test_bad_arguments_are_refused_on_the_host(lib, call):
 
 
 def test_the_part_table_formula_is_the_library_function(lib):
-    """the torch expression that fills part_start on the device against vlsa_cluster_pool_parts, around every boundary of both"""
-    from vlsa_amd.functional import cluster_pool_part_counts
-    tile, cap = lib.vlsa_cluster_pool_tile_rows(), lib.vlsa_cluster_pool_parts(1 << 62)
-    ns = [1, 2, tile - 1, tile, tile + 1, 2798, cap * tile - 1, cap * tile, cap * tile + 1, 20000, 50000, 10 ** 7, 2 ** 40]
-    assert cluster_pool_part_counts(torch.tensor(ns, dtype=torch.int64)).tolist() == [lib.vlsa_cluster_pool_parts(n) for n in ns]
+    """the one torch expression that fills every route's part_start on the device (``part_counts``, called by ``_ChunkPlan.part_table``
+    with the rows and the cap asked of the library) against the library's own *_parts(n), around every boundary of rows and cap"""
+    from vlsa_amd.functional import part_counts
+    routes = {"dsmil": (lib.vlsa_dsmil_part_rows, lib.vlsa_dsmil_parts), "cluster_pool": (lib.vlsa_cluster_pool_tile_rows, lib.vlsa_cluster_pool_parts),
+              "ilra": (lib.vlsa_ilra_pool_part_rows, lib.vlsa_ilra_pool_parts)}
+    for name, (rows_of, parts_of) in routes.items():
+        rows, cap = rows_of(), parts_of(1 << 62)
+        ns = [1, 2, rows - 1, rows, rows + 1, 2798, rows * cap - 1, rows * cap, rows * cap + 1, 20000, 50000, 10 ** 7, 2 ** 40]
+        want = [parts_of(n) for n in ns]
+        assert part_counts(torch.tensor(ns, dtype=torch.int64), rows, cap).tolist() == want, name
+        assert want[3:5] == [1, 2] and want[7:9] == [cap, cap] and want[6] == cap and want[-1] == cap, name
+    assert {k: (r(), p(1 << 62)) for k, (r, p) in routes.items()} == {"dsmil": (512, 64), "cluster_pool": (64, 128), "ilra": (256, 64)}
 
 
 def test_ids_that_match_no_cluster_become_minus_one_before_the_cast():

@@ -126,17 +126,30 @@ def test_a_row_of_no_cluster_may_hold_anything_in_the_forward():
 BATCH = [8, 2798, 17, 600, 257]
 
 
-@pytest.fixture(scope="module")
-def batch():
+# 64 bags, the table's last lane in use: 1 + (7 i) % 40 rows each, bag 63 raised to 130 rows = three forward tiles and parts, five
+# backward tiles
+BATCH64 = [1 + (7 * i) % 40 for i in range(63)] + [130]
+
+
+def _make_batch(sizes):
     m = AH.build_model(8, 4, 71, DEV)
-    xs = [make_rows(n, "bf16", 80 + i) for i, n in enumerate(BATCH)]
-    idss = [AC.make_ids(n, 8, 80 + i) for i, n in enumerate(BATCH)]
-    w = np.random.RandomState(72).standard_normal((len(BATCH), 4)).astype(np.float32)
+    xs = [make_rows(n, "bf16", 80 + i) for i, n in enumerate(sizes)]
+    idss = [AC.make_ids(max(n, 8), 8, 80 + i)[:n] for i, n in enumerate(sizes)]          # (a bag of fewer than 8 rows leaves clusters empty)
+    w = np.random.RandomState(72).standard_normal((len(sizes), 4)).astype(np.float32)
     return m, [_bag(x, "bf16") for x in xs], [torch.from_numpy(i) for i in idss], w
 
 
+@pytest.fixture(scope="module")
+def batch():
+    return _make_batch(BATCH)
+
+
 def test_batch_equals_single_calls_and_is_reproducible(batch):
-    m, bags, idss, w = batch
+    for tag, (m, bags, idss, w) in (("batch", batch), ("64 bags", _make_batch(BATCH64))):
+        _batch_equals_single_calls_and_is_reproducible(tag, m, bags, idss, w)
+
+
+def _batch_equals_single_calls_and_is_reproducible(tag, m, bags, idss, w):
     logits, hc, _, _, grads = _run(m, bags, idss, w)
     singles, gsum = [], None
     for i, (x, c) in enumerate(zip(bags, idss)):
@@ -146,10 +159,10 @@ def test_batch_equals_single_calls_and_is_reproducible(batch):
         singles.append(out.detach())
         g = [p.grad.detach().double() for p in AH.params_of(m)]
         gsum = g if gsum is None else [a + b for a, b in zip(gsum, g)]
-    assert torch.equal(logits, torch.cat(singles)), float((logits - torch.cat(singles)).abs().max())
-    AH.check_grads("batch vs the sum of single calls", grads, {k: g.cpu().numpy() for k, g in zip(AC.KEYS, gsum)})
+    assert torch.equal(logits, torch.cat(singles)), (tag, float((logits - torch.cat(singles)).abs().max()))
+    AH.check_grads(tag + " vs the sum of single calls", grads, {k: g.cpu().numpy() for k, g in zip(AC.KEYS, gsum)})
     again = _run(m, bags, idss, w)
-    assert torch.equal(again[0], logits) and torch.equal(again[1], hc) and all(torch.equal(a, b) for a, b in zip(again[4], grads))
+    assert torch.equal(again[0], logits) and torch.equal(again[1], hc) and all(torch.equal(a, b) for a, b in zip(again[4], grads)), tag
 
 
 def test_cpu_float_row_vector_ids_and_modes(batch):

@@ -189,6 +189,7 @@ _SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p]),
     "vlsa_vlfan_backward_dx": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vlsa_dsmil_part_rows": (c_int, []),
     "vlsa_dsmil_parts": (c_int, [c_int64]),
     "vlsa_dsmil_workspace_bytes": (c_size_t, [c_int, c_int]),
     "vlsa_dsmil_state_floats": (c_size_t, [c_int, c_int, c_void_p]),

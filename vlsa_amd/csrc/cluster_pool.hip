@@ -11,9 +11,10 @@
 //     packed by k_cp_prep into the workspace: 3 x mfma_f32_16x16x32_bf16 per fragment pair, fp32 accumulation.  Two terms (2^-17) put
 //     the worst pre of a 2 798-row bag 9e-7 off, too close to the 1e-6 band inside which the ReLU mask is allowed to differ.
 //   * fp32 rows take the fp32-input MFMA (16x16x4, an exact fp32 FMA chain) on the fp32 weights as they are.
-// Epilogue: the ReLU decisions leave as wave ballots -- 256 bits per row, bit j set iff pre_n[j] > 0 -- and the per-cluster sums are one
+// Epilogue: the ReLU decisions leave as wave ballots in the shared mask format (bag_table.h) and the per-cluster sums are one
 // more fp32 MFMA per accumulator register with the 0/1 matrix [cluster k][row] as the A operand: exact fp32 adds in a fixed order,
-// 16 running registers per lane for the whole part, no LDS, no atomics.  Ids outside [0, Kc) belong to no cluster; an empty cluster's
+// 16 running registers per lane for the whole part, no LDS, no atomics.  (Bag lookup, mask and MFMA wrappers: DESIGN.md, "Table-driven
+// kernels".)  Ids outside [0, Kc) belong to no cluster; an empty cluster's
 // row of hc is zero.  k_cp_merge adds a bag's parts in part order and divides by the count.  A row of no cluster enters the sums as
 // an exact 0 whatever it holds; a non-finite value in a row that HAS a cluster reaches all clusters of its tile (0 x Inf in the 0/1 MFMA),
 // and the backward multiplies every row of a tile, clustered or not, by its (possibly zero) dpre: the rows must be finite.
@@ -25,7 +26,7 @@
 // MFMA wants 8 rows of one feature per lane), builds the A fragments (dpre as a two-term bf16 split, 2^-17: the gradients are held
 // to 1e-4) once per workgroup and issues 2 (bf16 rows) or 3 (fp32 rows as hi + lo: hi hi, hi lo, lo hi) MFMAs per fragment pair.
 // The R <= 64 partials ([256, 512] + [256] floats each: at most 32.1 MiB) are added in split order by k_cp_reduce: bit-reproducible.
-#include "vlsa_common.h"
+#include "bag_table.h"
 
 namespace {
 using namespace vlsa;
@@ -35,21 +36,8 @@ constexpr int kTileF = 64;         // rows per forward tile
 constexpr int kChunk = 128;        // features per staged chunk of the forward
 constexpr int kMaxParts = 128;     // partial records per bag
 constexpr int kTileB = 32;         // rows per backward tile (one MFMA K step)
-constexpr int kMaxSplits = 64;     // row splits of the backward
 constexpr size_t kWpackBytes = (size_t)16 * 16 * 3 * 1024;
 constexpr int kDsLd = 80;          // floats per cluster row of the backward's dS table in LDS
-
-// the bag of block blk and the block's index within it
-__device__ __forceinline__ int find_bag(const int* start, int B, int blk, int* g, int* G) {
-    int b = 0;
-    while (b < B - 1 && blk >= start[b + 1]) ++b;
-    *g = blk - start[b];
-    *G = start[b + 1] - start[b];
-    return b;
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // wpack[((hg * 16 + ks) * 3 + term) * 1024 + lane * 16 + 2 e] = term of Wp[16 hg + (lane & 15)][32 ks + 8 (lane >> 4) + e]; grid 768 x 64
 __global__ __launch_bounds__(64) void k_cp_prep(const float* __restrict__ Wp, unsigned char* __restrict__ wpack) {
@@ -86,8 +74,8 @@ __global__ __launch_bounds__(kThreads) void k_cp_forward(const vlsa_bag_desc* __
     __shared__ __attribute__((aligned(16))) unsigned char xs[kTileF * F::kLd];
     __shared__ __attribute__((aligned(16))) int cids[kTileF];
     __shared__ unsigned int mt[kTileF * 8];
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     const T* X = static_cast<const T*>(bags[b].X);
     const long long N = bags[b].N, ldx = bags[b].ldx, roff = row_off[b];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), gq = lane >> 4, i16 = lane & 15;
@@ -179,11 +167,7 @@ __global__ __launch_bounds__(kThreads) void k_cp_forward(const vlsa_bag_desc* __
                 unsigned long long bal[4];
 #pragma unroll
                 for (int hg = 0; hg < 4; ++hg) bal[hg] = __builtin_amdgcn_ballot_w64(acc[rt][hg][e] > 0.f);
-                if (mask != nullptr && i16 < 2) {       // word 2 w + i16 of the row: units 64 w + 32 i16 .. + 31
-                    const unsigned long long lo = i16 ? bal[2] : bal[0], hi = i16 ? bal[3] : bal[1];
-                    mt[(rt * 16 + 4 * gq + e) * 8 + 2 * w + i16] =
-                        (unsigned int)((lo >> (16 * gq)) & 0xffffull) | ((unsigned int)((hi >> (16 * gq)) & 0xffffull) << 16);
-                }
+                if (mask != nullptr && i16 < 2) mt[(rt * 16 + 4 * gq + e) * 8 + 2 * w + i16] = relu_mask_word(bal, i16, gq);
                 const float sel = cv[e] == i16 ? 1.f : 0.f;
                 const bool in = cv[e] >= 0;             // a row of no cluster enters as 0, so that an Inf or NaN in it stays out of the sums
 #pragma unroll
@@ -253,10 +237,10 @@ template <typename T> struct BwdRegs {
 template <typename T>
 __device__ __forceinline__ void bwd_load(BwdRegs<T>& r, const vlsa_bag_desc* bags, int B, const int* tile_start, const long long* row_off,
                                          const int* ids, const unsigned int* mask, int Kc, int slice, int t, int tid) {
-    int lt, nt;
-    const int b = find_bag(tile_start, B, t, &lt, &nt);
+    const BagSpan tile = bag_span(tile_start, B, t);       // (t and the branches around the calls are block-uniform)
+    const int b = tile.b;
     const T* X = static_cast<const T*>(bags[b].X);
-    const long long N = bags[b].N, ldx = bags[b].ldx, roff = row_off[b], row0 = (long long)lt * kTileB;
+    const long long N = bags[b].N, ldx = bags[b].ldx, roff = row_off[b], row0 = (long long)tile.idx * kTileB;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -278,6 +262,7 @@ __device__ __forceinline__ void bwd_load(BwdRegs<T>& r, const vlsa_bag_desc* bag
         const int id = ids[roff + row0 + tid];
         r.cid = (id < 0 || id >= Kc) ? -1 : id;
     }
+    // the two mask words (bag_table.h) of this hidden slice of 64 units
     if (tid < 2 * kTileB && row0 + (tid >> 1) < N) r.mw = mask[(size_t)(roff + row0 + (tid >> 1)) * 8 + 2 * slice + (tid & 1)];
 }
 
@@ -349,8 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_cp_backward(const vlsa_bag_desc* _
     BwdRegs<T> regs;
     if (split < n_tiles) bwd_load<T>(regs, bags, B, tile_start, row_off, ids, mask, Kc, slice, split, tid);
     for (int t = split; t < n_tiles; t += R) {
-        int lt, nt;
-        const int b = find_bag(tile_start, B, t, &lt, &nt);
+        const int b = bag_span(tile_start, B, t).b;
         bwd_publish<T>(regs, lds, tid);
         if (b != table_bag) {            // dS of this bag and slice: dhc / cnt, zero for an empty cluster
             for (int i = tid; i < kMaxK * 64; i += kThreads) {
@@ -429,11 +413,6 @@ __global__ __launch_bounds__(kThreads) void k_cp_reduce(int R, const float* __re
         for (int r = 0; r < R; ++r) a += pdb[(size_t)r * kH + t];
         dbp[t] = a;
     }
-}
-
-int splits_of(int n_tiles) {
-    const int r = (n_tiles + 3) / 4;
-    return r < 1 ? 1 : (r > kMaxSplits ? kMaxSplits : r);
 }
 
 int check_common(const void* bag_desc, int B, int x_dtype, int D, int H, int Kc, const int* table, int n_table) {

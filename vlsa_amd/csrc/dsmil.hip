@@ -14,13 +14,13 @@
 //
 // A bag of N rows is cut into vlsa_dsmil_parts(N) partial records -- a function of N alone, so a bag's result does not depend on the
 // batch it travels in (a batch of B bags equals B single calls bit for bit).  Part g of a bag with G parts takes the row tiles
-// g, g + G, ... of that bag.
+// g, g + G, ... of that bag.  A workgroup finds its bag and part with bag_span (bag_table.h; DESIGN.md, "Table-driven kernels").
 //
 // Lane layout of the dot products: 16 lanes share a row, lane j holds the four 8-feature chunks (k * 16 + j), k = 0..3; the C
 // partial sums of a row are reduced over the 16 lanes by an exchange that halves the value count per step (15 shuffles for 16
 // classes) and leaves class (j * CP / 16) in lane j.  The weighted sums run as a register-tiled [CP x rows] x [rows x 512] product
 // out of an LDS copy of the row tile.
-#include "vlsa_common.h"
+#include "bag_table.h"
 
 namespace {
 using namespace vlsa;
@@ -30,6 +30,7 @@ constexpr int kD = 512, kH = 256, kMaxC = 16, kThreads = 256;
 constexpr int rows_per_group(int cp) { return cp <= 4 ? 4 : 2; }
 constexpr int kTileB = 32;        // rows per tile of the kernels that keep the tile in LDS (2 rows per group)
 constexpr float kInvSqrtH = 0.0625f;
+constexpr int kPartRows = 512, kMaxParts = 64;     // rows per partial record of a bag, records per bag
 
 
 __device__ __forceinline__ void load8(const float* p, float* o) {
@@ -50,15 +51,6 @@ __device__ __forceinline__ void store8(__bf16* p, const float* o) {      // (exa
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (__bf16)o[e];
     *reinterpret_cast<bf16x8*>(p) = v;
-}
-
-// the bag of block blk and the block's part index within it
-__device__ __forceinline__ int find_bag(const int* part_start, int B, int blk, int* g, int* G) {
-    int b = 0;
-    while (b < B - 1 && blk >= part_start[b + 1]) ++b;
-    *g = blk - part_start[b];
-    *G = part_start[b + 1] - part_start[b];
-    return b;
 }
 
 // R rows of a 16-lane group into registers: x[r][k * 8 + e] = feature (k * 16 + j) * 8 + e of row min(row0 + r, N - 1)
@@ -125,8 +117,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_scores(const vlsa_bag_desc* 
     __shared__ float W[CP * kD];
     __shared__ float rv[16][CP];
     __shared__ int ri[16][CP];
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     fill_queries(W, Wc, C, CP, 1.f);
     __syncthreads();
     const T* X = static_cast<const T*>(bags[b].X);
@@ -316,8 +308,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_aggregate(const vlsa_bag_des
     float* S = reinterpret_cast<float*>(xt + kTileB * ld);
     float* Mrun = S + kTileB * CP;
     float* Scale = Mrun + kMaxC;
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     fill_queries(U, u + (size_t)b * C * kD, C, CP, kLog2e);
     if (threadIdx.x < kMaxC) Mrun[threadIdx.x] = -INFINITY;
     __syncthreads();
@@ -458,8 +450,8 @@ template <typename T, int CP>
 __global__ __launch_bounds__(kThreads) void k_dsmil_attn(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
                                                          const float* m2, const float* l, float* attn, const long long* a_off) {
     __shared__ float U[CP * kD];
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     fill_queries(U, u + (size_t)b * C * kD, C, CP, kLog2e);
     __syncthreads();
     const T* X = static_cast<const T*>(bags[b].X);
@@ -525,8 +517,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_bwd_stream(const vlsa_bag_de
     float* DZ = U + CP * kD;
     T* xt = reinterpret_cast<T*>(DZ + CP * kD);
     float* S = reinterpret_cast<float*>(xt + kTileB * ld);
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     fill_queries(U, u + (size_t)b * C * kD, C, CP, kLog2e);
     fill_queries(DZ, dz + (size_t)b * C * kD, C, CP, 1.f);
     __syncthreads();
@@ -728,9 +720,11 @@ int check_common(const void* bag_desc, int B, int x_dtype, int D, int H, int C, 
 
 }  // namespace
 
+extern "C" int vlsa_dsmil_part_rows(void) { return kPartRows; }
+
 extern "C" int vlsa_dsmil_parts(int64_t N) {
-    const int64_t g = (N + 511) / 512;
-    return (int)(g < 1 ? 1 : (g > 64 ? 64 : g));
+    const int64_t g = (N + kPartRows - 1) / kPartRows;
+    return (int)(g < 1 ? 1 : (g > kMaxParts ? kMaxParts : g));
 }
 
 extern "C" size_t vlsa_dsmil_workspace_bytes(int n_parts, int C) {

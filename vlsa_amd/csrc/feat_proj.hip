@@ -17,7 +17,7 @@
 //     stored fp32 row-major -- the bag the fp32 streaming / scoring kernels then consume.
 // Roofline: MFMA-bound, 2 terms x 2 x 512 x 512 = 1.05 MFLOP per patch (the same as the gated attention scores) plus 2 KB
 // per patch written.
-#include "vlsa_common.h"
+#include "feat_proj.h"
 
 #ifndef FP_XBUF
 #define FP_XBUF 1
@@ -26,26 +26,12 @@
 namespace vlsa {
 
 namespace fp {
-constexpr int kD = 512;                           // input and output width
-constexpr int kSteps = 16;                        // K steps of 32
-constexpr int kNF = 8;                            // weight fragments per step and wave: 4 column tiles x (hi, lo)
 constexpr int kMaxRows = 128;
 constexpr int kXBuf = kMaxRows * 64;              // one K step of the tile, one bf16 image: 128 rows x 32 bf16 = 8 KiB
 constexpr int kScrOff = 4 * kXBuf;                // 2 buffers x (hi, lo image)
 constexpr int kStatOff = kScrOff + 8 * kMaxRows * 4;
 constexpr int kLds = kStatOff + kMaxRows * 4;     // 37,376 B
 }  // namespace fp
-
-struct FeatProjLayout {
-    size_t wpack, bias, gamma, beta, total;
-    __host__ __device__ FeatProjLayout() {
-        wpack = 0;
-        bias = wpack + (size_t)8 * fp::kSteps * fp::kNF * 1024;   // 1 MiB
-        gamma = bias + fp::kD * 4;
-        beta = gamma + fp::kD * 4;
-        total = beta + fp::kD * 4;
-    }
-};
 
 // packed[((w * 16 + ks) * 8 + f) * 1024 + lane * 16 + 2 e] = term(f & 1) of W[64 w + 16 (f >> 1) + (lane & 15)][32 ks + 8 (lane >> 4) + e]
 // grid = 8 * 16 * 8 workgroups of 64 threads.
@@ -75,15 +61,6 @@ __global__ __launch_bounds__(64) void k_prepare_featproj(const float* __restrict
             pe[i] = beta ? beta[i] : 0.f;
         }
     }
-}
-
-// sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), result in every lane
-__device__ __forceinline__ float fp_row16_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));  // row_ror:8
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));  // row_ror:1
-    return v;
 }
 
 // One tile of 16 RT rows of ONE bag, rows [row0, row0 + 16 RT) of X [N, ldx], by the whole workgroup (512 threads): the body of both
@@ -223,7 +200,7 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float s = fp_row16_sum((acc[rt][0][r] + acc[rt][1][r]) + (acc[rt][2][r] + acc[rt][3][r]));
+            const float s = row16_sum((acc[rt][0][r] + acc[rt][1][r]) + (acc[rt][2][r] + acc[rt][3][r]));
             if (i16 == 0) scr[w * ROWS + 16 * rt + 4 * g + r] = s;
         }
     __syncthreads();
@@ -243,7 +220,7 @@ __device__ __forceinline__ void fp_tile(unsigned char* __restrict__ smem, const 
         for (int ct = 0; ct < 4; ++ct) acc[rt][ct] -= mean;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float q = fp_row16_sum((acc[rt][0][r] * acc[rt][0][r] + acc[rt][1][r] * acc[rt][1][r]) +
+            const float q = row16_sum((acc[rt][0][r] * acc[rt][0][r] + acc[rt][1][r] * acc[rt][1][r]) +
                                          (acc[rt][2][r] * acc[rt][2][r] + acc[rt][3][r] * acc[rt][3][r]));
             if (i16 == 0) scr[w * ROWS + 16 * rt + 4 * g + r] = q;     // (every wave's reads of scr are behind the barrier above)
         }
@@ -299,9 +276,7 @@ __global__ __launch_bounds__(512) void k_feat_proj_bags(const vlsa_bag_desc* __r
                                                          const long long* __restrict__ row_off, const unsigned char* __restrict__ prep,
                                                          float eps, float* __restrict__ Y, float* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63, t = blockIdx.x;
-    const int ts = lane < B ? tile_start[lane] : 0x7fffffff;
-    const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1);
+    const int t = blockIdx.x, b = bag_of(tile_start, B, t);
     if (b < 0) return;
     const vlsa_bag_desc bag = bags[b];
     const long long row0 = (long long)(t - tile_start[b]) * (16 * RT);

@@ -1,7 +1,7 @@
 // Shared between gated_scores.hip (the score kernels of rounds 1-4) and gated_scores_tile.hip (round 5: both operands through
 // LDS-DMA): the packed-weight block layout, the bag table of a batched launch, the activation helpers.
 #pragma once
-#include "vlsa_common.h"
+#include "bag_table.h"
 
 namespace vlsa {
 
@@ -48,14 +48,6 @@ __device__ __forceinline__ float gate_act3(float au, float av) {
 __device__ __forceinline__ float tanh_act3(float au) {
     const float u = fast_exp2(__builtin_amdgcn_fmed3f(au, -1.0e30f, 43.f));
     return (1.f - u) * __builtin_amdgcn_rcpf(1.f + u);
-}
-// sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), result in every lane: four full-rate VALU adds
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));  // row_ror:8
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));  // row_ror:1
-    return v;
 }
 
 struct GsBatch {

@@ -150,9 +150,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_gated_scores(const void* __restr
     const int nrt = FULL ? RT : (rows_per_tile >> 4);
     int tile = HALVES == 1 ? bid : bid < nfull ? ((bid >> 4) << 3) + (bid & 7) : bid >> 1;
     unsigned int drop_seed = bt.drop_seed;
-    if (bt.bags != nullptr) {   // one vector load of the (<= 65-entry) tile table + a ballot instead of a dependent scalar search
-        const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
-        const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= tile)) - 1;
+    if (bt.bags != nullptr) {
+        const int b = bag_of(bt.tile_start, bt.B, tile);
         if (GATED && bt.seed_word != nullptr) drop_seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
         const vlsa_bag_desc bag = bt.bags[b];
         Xv = bag.X;

@@ -179,8 +179,7 @@ __global__ __launch_bounds__(512, 2) void k_scores_tile_p(const void* __restrict
         int tile = t;
         unsigned int seed = bt.drop_seed;
         if (bt.bags != nullptr) {
-            const int ts = lane < bt.B ? bt.tile_start[lane] : 0x7fffffff;
-            const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
+            const int b = bag_of(bt.tile_start, bt.B, t);
             if (GATED && bt.seed_word != nullptr) seed = bag_drop_seed((unsigned int)*bt.seed_word, b);
             const vlsa_bag_desc bag = bt.bags[b];
             Xv = bag.X;

@@ -18,11 +18,11 @@
 // the same MFMA chain; dE = sum c x (partials per
 // part, added in part order over all bags) and, for packed rows, dX_n = sum_p a_p(n) g_p + c_p(n) e_p.
 // Row map forward: per tile u and the gate pre-activation share the staged rows; u goes through LDS for the 256 -> 256 product; the
-// ReLU decisions t > 0 leave as 256 bits per row.
+// ReLU decisions t > 0 leave in the shared mask format (bag_table.h; DESIGN.md, "Table-driven kernels", also for the bag lookup).
 // Row map backward: recomputes u, t and the gate from the rows, READS the mask, stages u, du, ds, dt ([sum N_b, 256] fp32 each) in the
 // workspace, forms du = do + Wo^T dt (and dX = Wq^T du + Wg^T ds for packed rows) in the same kernel, then three [256, n] x [n, D]
 // products (k_rm_wgrad: row splits in registers, partials added in split order) and the column sums per bag.
-#include "vlsa_common.h"
+#include "bag_table.h"
 
 namespace {
 using namespace vlsa;
@@ -36,17 +36,7 @@ constexpr int kXld = kChunk + 4;   // floats per LDS row of a chunk
 constexpr int kUld = kH + 4;       // floats per LDS row of a [32][256] tile read as an A operand
 constexpr int kGld = kH + 16;      // ... read as a B operand (row stride = 16 banks)
 constexpr int kWld = kChunk + 16;
-constexpr int kMaxSplits = 64, kSegs = 8;
-
-__device__ __forceinline__ int find_bag(const int* start, int B, int blk, int* g, int* G) {
-    int b = 0;
-    while (b < B - 1 && blk >= start[b + 1]) ++b;
-    *g = blk - start[b];
-    *G = start[b + 1] - start[b];
-    return b;
-}
-
-__device__ __forceinline__ f32x4 mfma_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+constexpr int kSegs = 8;
 
 // rows row0 .. row0 + rows - 1, features c0 .. c0 + CH - 1 as fp32 into xs (ld floats per row); rows past the bag's end are zeros
 template <typename T>
@@ -153,8 +143,8 @@ __global__ __launch_bounds__(kThreads) void k_ip_forward(const vlsa_bag_desc* __
     __shared__ __attribute__((aligned(16))) float sp_[4 * 16 * 16];
     float_ma* xs = xs_;
     float_ma* sp = sp_;
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     const RowSrc src = row_src<D>(bags, row_off, xp, b);
     const T* X = static_cast<const T*>(src.X);
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), gq = lane >> 4, i16 = lane & 15;
@@ -248,8 +238,8 @@ __global__ __launch_bounds__(kThreads) void k_ip_backward(const vlsa_bag_desc* _
     float_ma* gp = gp_;
     float_ma* at = at_;
     float_ma* ct = ct_;
-    int g, G;
-    const int b = find_bag(part_start, B, blockIdx.x, &g, &G);
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    const int b = part.b, g = part.idx, G = part.count;
     const RowSrc src = row_src<D>(bags, row_off, xp, b);
     const T* X = static_cast<const T*>(src.X);
     const float* Gb = dZ + (size_t)b * P * D;
@@ -379,10 +369,10 @@ __global__ __launch_bounds__(kThreads) void k_rm_forward(const vlsa_bag_desc* __
     __shared__ unsigned int mt[kTile * 8];
     float_ma* xs = xs_;
     float_ma* us = us_;
-    int lt, nt;
-    const int b = find_bag(tile_start, B, blockIdx.x, &lt, &nt);
+    const BagSpan tile = bag_span(tile_start, B, blockIdx.x);
+    const int b = tile.b;
     const RowSrc src = row_src<D>(bags, row_off, xp, b);
-    const long long row0 = (long long)lt * kTile;
+    const long long row0 = (long long)tile.idx * kTile;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), gq = lane >> 4, i16 = lane & 15;
     f32x4 u[2][4], s[2][4], t[2][4];
     rm_u_s<T, D>(u, s, xs, src, row0, Wq, btil + (size_t)b * kH, Wg, bg, tid, w, gq, i16);
@@ -398,10 +388,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_forward(const vlsa_bag_desc* __
             unsigned long long bal[4];
 #pragma unroll
             for (int hg = 0; hg < 4; ++hg) bal[hg] = __builtin_amdgcn_ballot_w64(t[rt][hg][e] > 0.f);
-            if (i16 < 2) {                     // word 2 w + i16 of the row: units 64 w + 32 i16 .. + 31
-                const unsigned long long lo = i16 ? bal[2] : bal[0], hi = i16 ? bal[3] : bal[1];
-                mt[row * 8 + 2 * w + i16] = (unsigned int)((lo >> (16 * gq)) & 0xffffull) | ((unsigned int)((hi >> (16 * gq)) & 0xffffull) << 16);
-            }
+            if (i16 < 2) mt[row * 8 + 2 * w + i16] = relu_mask_word(bal, i16, gq);
             if (row0 + row < src.N) {
 #pragma unroll
                 for (int hg = 0; hg < 4; ++hg) {
@@ -432,10 +419,10 @@ __global__ __launch_bounds__(kThreads) void k_rm_backward(const vlsa_bag_desc* _
     __shared__ __attribute__((aligned(16))) float us_[kTile * kUld];
     float_ma* xs = xs_;
     float_ma* us = us_;
-    int lt, nt;
-    const int b = find_bag(tile_start, B, blockIdx.x, &lt, &nt);
+    const BagSpan tile = bag_span(tile_start, B, blockIdx.x);
+    const int b = tile.b;
     const RowSrc src = row_src<D>(bags, row_off, xp, b);
-    const long long row0 = (long long)lt * kTile;
+    const long long row0 = (long long)tile.idx * kTile;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), gq = lane >> 4, i16 = lane & 15;
     float* wu = ws;
     float* wdu = ws + (size_t)total * kH;
@@ -461,7 +448,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_backward(const vlsa_bag_desc* _
                 float dov = 0.f, dsv = 0.f, dtv = 0.f;
                 if (ok) {
                     const float g = dOut[grow * kH + unit];
-                    const bool bit = (mask[grow * 8 + (unit >> 5)] >> (unit & 31)) & 1u;
+                    const bool bit = relu_mask_bit(mask + grow * 8, unit);
                     const float uv = u[rt][hg][e], sv = s[rt][hg][e];
                     const float o = uv + (bit ? t[rt][hg][e] : 0.f);
                     const float sig = 1.f / (1.f + expf(-sv));
@@ -532,10 +519,9 @@ __global__ __launch_bounds__(kThreads) void k_rm_wgrad(const vlsa_bag_desc* __re
 #pragma unroll
         for (int fg = 0; fg < 8; ++fg) acc[hg][fg] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int t = split; t < n_tiles; t += R) {
-        int lt, nt;
-        const int b = find_bag(tile_start, B, t, &lt, &nt);
-        const RowSrc src = row_src<D>(bags, row_off, xp, b);
-        const long long row0 = (long long)lt * kTile;
+        const BagSpan tile = bag_span(tile_start, B, t);       // (t is block-uniform, the loop bound too)
+        const RowSrc src = row_src<D>(bags, row_off, xp, tile.b);
+        const long long row0 = (long long)tile.idx * kTile;
         __syncthreads();
         stage_tile<float>(gs, kGld, G + (size_t)src.roff * kH, kH, row0, src.N, 0, kH, kTile, tid);
         stage_tile<T>(xs, kWld, static_cast<const T*>(src.X), src.ldx, row0, src.N, f0, kChunk, kTile, tid);
@@ -599,11 +585,6 @@ __global__ __launch_bounds__(kThreads) void k_rm_colfold(int B, const float* __r
         }
     dbg[t] = g;
     dbo[t] = o;
-}
-
-int splits_of(int n_tiles) {
-    const int r = (n_tiles + 3) / 4;
-    return r < 1 ? 1 : (r > kMaxSplits ? kMaxSplits : r);
 }
 
 // 0: bf16 bag rows, 1: fp32 bag rows (D = 512); 2: packed fp32 rows (D = 256); < 0: the error

@@ -27,7 +27,8 @@
 //     split into bf16 hi + lo images on the fly (32-row tiles, 3 product terms).  dH is split hi + lo as well.
 // MFMA-bound: per row 2 x (512 x H) recompute + 2 x (512 x H) for dW, both as 2 bf16 terms (H = 512 gated, 256 tanh, 512
 // projecter): 2.1 MFLOP per row for the gated scores = 4 x the algorithmic forward.
-#include "vlsa_common.h"
+#include "feat_proj.h"
+#include "gated_scores.h"
 
 namespace vlsa {
 
@@ -119,8 +120,7 @@ __global__ __launch_bounds__(512) void k_mlp_backward(const MbArgs a) {
     // ---- tile lookup + register staging of a tile's rows -------------------------------------------------------------------
     struct Tile { const unsigned char* x; const float* dy; const float* rv; long long ldx, lddy; int nrows, b; unsigned int rid, seed; float m2, linv; };
     auto find = [&](int t) -> Tile {
-        const int ts = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
-        const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= t)) - 1;
+        const int b = bag_of(a.tile_start, a.B, t);       // (t walks the block's own range: block-uniform)
         const vlsa_bag_desc bag = a.bags[b];
         const long long row0 = (long long)(t - a.tile_start[b]) * ROWS;
         Tile r;
@@ -480,8 +480,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const vlsa_bag_des
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= total) return;
-    const long long ro = lane < B ? row_off[lane] : 0x7fffffffffffffffll;
-    const int b = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(ro <= row)) - 1);
+    const int b = bag_of(row_off, B, row);            // (row is the wave's own: wave-uniform)
     if (b < 0) return;
     const vlsa_bag_desc g = dyb[b];
     const long long r = row - row_off[b];
@@ -494,19 +493,6 @@ __global__ __launch_bounds__(256) void k_ln_bwd_rowstats_bags(const vlsa_bag_des
 using namespace vlsa;
 
 namespace {
-struct GatedPrepOffsets {      // mirrors GatedPrepLayout (gated_scores.hip)
-    size_t wpack, ba, bg, w2, c;
-    explicit GatedPrepOffsets(int gated) {
-        wpack = 0;
-        ba = wpack + (size_t)2 * 8 * 16 * (gated ? 4 : 2) * 1024;
-        bg = ba + 256 * 4;
-        w2 = bg + 256 * 4;
-        c = w2 + 256 * 4;
-    }
-};
-struct FeatProjOffsets {       // mirrors FeatProjLayout (feat_proj.hip)
-    size_t wpack = 0, bias = (size_t)8 * 16 * 8 * 1024, gamma = bias + 512 * 4, beta = gamma + 512 * 4;
-};
 int chunks_for(int n_tiles, int nsl) {
     int C = 256 / nsl;
     if (n_tiles < C) C = n_tiles;
@@ -541,7 +527,7 @@ extern "C" int vlsa_attn_scores_backward(const void* bag_desc, int B, int x_dtyp
     if (!bag_desc || !prep || !tile_start || !da || !a_off || !ws || !dW || !dvec || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     const int mode = gated ? mb::kGated : mb::kTanh, nsl = gated ? 4 : 2, U = gated ? 512 : 256;
-    const GatedPrepOffsets L(gated ? 1 : 0);
+    const GatedPrepLayout L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
     a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
@@ -595,7 +581,7 @@ extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_
         return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     const int nsl = gated ? 4 : 2, U = gated ? 512 : 256;
-    const GatedPrepOffsets L(gated ? 1 : 0);
+    const GatedPrepLayout L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
     a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
@@ -644,7 +630,7 @@ extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_
 extern "C" int vlsa_feat_project_rowstats(const float* dy, int64_t lddy, const float* y, int64_t ldy, int64_t N, const void* prep,
                                           float* stats, void* stream) {
     if (!dy || !y || !prep || !stats || N < 1 || lddy < 512 || ldy < 512) return VLSA_EINVAL;
-    const FeatProjOffsets L;
+    const FeatProjLayout L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     hipLaunchKernelGGL(k_ln_bwd_rowstats, dim3((unsigned int)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, (long long)lddy, y,
                        (long long)ldy, (long long)N, reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta),
@@ -658,7 +644,7 @@ extern "C" int vlsa_feat_project_rowstats(const float* dy, int64_t lddy, const f
 extern "C" int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, const float* y, const int64_t* row_off, int64_t total_rows,
                                                 const void* prep, float* stats, void* stream) {
     if (!dy_desc || !y || !row_off || !prep || !stats || B < 1 || B > 64 || total_rows < 1) return VLSA_EINVAL;
-    const FeatProjOffsets L;
+    const FeatProjLayout L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     hipLaunchKernelGGL(k_ln_bwd_rowstats_bags, dim3((unsigned int)((total_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const vlsa_bag_desc*>(dy_desc), B, reinterpret_cast<const long long*>(row_off), y, (long long)total_rows,
@@ -675,7 +661,7 @@ extern "C" int vlsa_feat_project_backward(const void* bag_desc, const void* dy_d
     if (!bag_desc || !dy_desc || !prep || !tile_start || !stats || !row_off || !ws || !dW || !dvec || B < 1 || B > 64 || n_tiles < 1)
         return VLSA_EINVAL;
     if (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32) return VLSA_EUNSUPPORTED;
-    const FeatProjOffsets L;
+    const FeatProjLayout L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     MbArgs a{};
     a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
@@ -765,9 +751,7 @@ __global__ __launch_bounds__(512) void k_attn_scores_dx(const AdxArgs a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i16 = lane & 15;
     const int t = blockIdx.x;
-    // tile lookup
-    const int tsv = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
-    const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(tsv <= t)) - 1;
+    const int b = bag_of(a.tile_start, a.B, t);
     const vlsa_bag_desc bag = a.bags[b], ob = a.dxs[b];
     const long long row0 = (long long)(t - a.tile_start[b]) * ROWS;
     const int nrows = (int)((bag.N - row0) < ROWS ? (bag.N - row0) : ROWS);
@@ -971,7 +955,7 @@ static int attn_scores_backward_dx_impl(const void* bag_desc, const void* dx_des
     if (!bag_desc || !dx_desc || !prep || !prep_t || !tile_start || !da || !a_off || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
     if ((aw == nullptr) != (dpooled == nullptr)) return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
-    const GatedPrepOffsets L(gated ? 1 : 0);
+    const GatedPrepLayout L(gated ? 1 : 0);
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     AdxArgs a{};
     a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);

@@ -144,10 +144,7 @@ __global__ __launch_bounds__(kLossThreads) void k_surv_loss(const float* __restr
 // workgroup and pass.  Same formulas; the cumulative sums keep the bin order (see row16_prefix), plain sums run in tree order.  Inside the training
 // step: 12.7 -> 4.7 us = the floor of a launch (the loops above are ~500 dependent LDS accesses on one wave).
 #define VLSA_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true))
-__device__ __forceinline__ float row16_sum(float v) {
-    v += VLSA_DPP(v, 0x128); v += VLSA_DPP(v, 0x124); v += VLSA_DPP(v, 0x122); v += VLSA_DPP(v, 0x121);      // row_ror 8, 4, 2, 1
-    return v;
-}
+// (row16_sum: vlsa_common.h)
 __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, VLSA_DPP(v, 0x128)); v = fmaxf(v, VLSA_DPP(v, 0x124)); v = fmaxf(v, VLSA_DPP(v, 0x122)); v = fmaxf(v, VLSA_DPP(v, 0x121));
     return v;

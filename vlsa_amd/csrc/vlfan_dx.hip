@@ -22,7 +22,7 @@
 //     the bag table (its 4 waves = 4 x 16 rows of the same bag) and reloads dout only when the bag changes.
 // All products are exact f32 (v_mfma_f32_16x16x4_f32): 512 steps x 32 cycles per 16-row tile = 6.8 us per wave-tile, i.e.
 // ~21 us per 50k-patch bag on 1024 waves -- about the HBM time of the 205 MB it moves (26 us at 8 TB/s).
-#include "vlsa_common.h"
+#include "bag_table.h"
 
 namespace vlsa {
 
@@ -69,8 +69,7 @@ __global__ __launch_bounds__(256) void k_vlfan_dx(const DxArgs a) {
 
     struct Tile { const float* x; float* dxo; long long ldx, lddx; int nrows, bag; };
     auto find = [&](int s) -> Tile {
-        const int ts = lane < a.B ? a.tile_start[lane] : 0x7fffffff;
-        const int b = __builtin_popcountll(__builtin_amdgcn_ballot_w64(ts <= s)) - 1;
+        const int b = bag_of(a.tile_start, a.B, s);
         const vlsa_bag_desc bag = a.bags[b], o = a.dxs[b];
         const long long row0 = (long long)(s - a.tile_start[b]) * 64 + 16 * w;
         Tile t;

@@ -1311,6 +1311,13 @@ def attn_scores_autograd(X2: torch.Tensor, fused: "FusedAttnScores", Wa, ba, Wg,
     return _AttnScoresFn.apply(X2, fused, Wa, ba, Wg, bg, w2, c, float(drop_p or 0.0), int(seed or 0))
 
 
+def part_counts(n: torch.Tensor, rows: int, cap: int) -> torch.Tensor:
+    """clamp(ceil(n / rows), 1, cap) of every entry of an integer tensor of bag sizes, on the tensor's own device: what the library's
+    vlsa_dsmil_parts, vlsa_cluster_pool_parts and vlsa_ilra_pool_parts give for ``rows`` = their ``*_part_rows()`` / ``*_tile_rows()``
+    and ``cap`` = their answer for a bag of 2^62 rows"""
+    return torch.clamp(torch.div(n + (rows - 1), rows, rounding_mode="floor"), 1, cap)
+
+
 def _chunk_len(bags) -> int:
     if not (1 <= len(bags) <= 64):
         raise ValueError("1..64 bags per call")
@@ -1327,6 +1334,17 @@ class _ChunkPlan:
 
     desc = property(lambda self: self.tables.desc)
     a_off = property(lambda self: self.tables.row_off)
+
+    def part_table(self, rows_of, parts_of) -> None:
+        """part_start [B + 1] (int32) and n_parts of a route whose bags own ``parts_of(N_b)`` partial records each: the two host-side
+        queries of the library (``vlsa_*_part_rows`` / ``*_tile_rows`` and ``vlsa_*_parts``).  n_parts, the launch's grid, is the library's
+        own sum; the table is ``part_counts`` of the descriptor's row counts with the rows and the cap asked of the library (its answer for
+        a bag of 2^62 rows), derived on the device by in-stream ops: the two cannot drift apart, and a plan may be built inside a
+        graph capture once the descriptor is up."""
+        n = self.desc[:, 1]
+        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
+        self.part_start[1:] = torch.cumsum(part_counts(n, int(rows_of()), int(parts_of(1 << 62))), 0)
+        self.n_parts = sum(int(parts_of(n)) for n in self.sizes)
 
     @classmethod
     def of(cls, bags, *args):
@@ -1948,10 +1966,7 @@ class DsmilBagsPlan(_ChunkPlan):
     def __init__(self, bags):
         lib = nat.load()
         super().__init__(_chunk_tables(bags, "the batched DSMIL route over a plain list of bags"))
-        self.n_parts = sum(int(lib.vlsa_dsmil_parts(n)) for n in self.sizes)
-        n = self.desc[:, 1]
-        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
-        self.part_start[1:] = torch.cumsum(torch.clamp(torch.div(n + 511, 512, rounding_mode="floor"), 1, 64), 0)   # vlsa_dsmil_parts
+        self.part_table(lib.vlsa_dsmil_part_rows, lib.vlsa_dsmil_parts)
 
 
 def dsmil_state_views(state: torch.Tensor, B: int, C: int) -> dict:
@@ -2024,14 +2039,6 @@ def dsmil_bags(bags, Wc, bc, Wq, bq, Wv, bv, Wf, bf, drop_p: float = 0.0, seed_w
 
 
 # ---- DeepAttnMISL's cluster layer (model/deepmil.py:565-577): phi + per-cluster mean over a table of bags -------------------------
-def cluster_pool_part_counts(n: torch.Tensor) -> torch.Tensor:
-    """vlsa_cluster_pool_parts of every entry of an integer tensor of bag sizes, on the tensor's own device: the tile and the cap on
-    the parts are the library's (its answer for a bag of 2^62 rows), so the table and the launch's grid cannot drift apart"""
-    lib = nat.load()
-    tile, cap = int(lib.vlsa_cluster_pool_tile_rows()), int(lib.vlsa_cluster_pool_parts(1 << 62))
-    return torch.clamp(torch.div(n + (tile - 1), tile, rounding_mode="floor"), 1, cap)
-
-
 class ClusterPoolPlan(_ChunkPlan):
     """Device tables of one chunk of <= 64 bags for vlsa_cluster_pool_forward_batch / _backward_batch: the descriptor table, the row
     offsets, part_start [B + 1] (bag b owns vlsa_cluster_pool_parts(N_b) partial records -- a function of N_b alone) and the
@@ -2041,10 +2048,7 @@ class ClusterPoolPlan(_ChunkPlan):
     def __init__(self, bags):
         lib = nat.load()
         super().__init__(_chunk_tables(bags, "the batched DeepAttnMISL route over a plain list of bags"))
-        self.n_parts = sum(int(lib.vlsa_cluster_pool_parts(n)) for n in self.sizes)
-        n = self.desc[:, 1]
-        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
-        self.part_start[1:] = torch.cumsum(cluster_pool_part_counts(n), 0)
+        self.part_table(lib.vlsa_cluster_pool_tile_rows, lib.vlsa_cluster_pool_parts)
         self.ts_b, self.n_tiles_b = self.tables.tile_start(int(lib.vlsa_cluster_pool_backward_tile_rows()))
 
 
@@ -2145,11 +2149,7 @@ class IlraPlan(_ChunkPlan):
     def __init__(self, bags):
         lib = nat.load()
         super().__init__(_chunk_tables(bags, "the batched ILRA route over a plain list of bags"))
-        self.n_parts = sum(int(lib.vlsa_ilra_pool_parts(n)) for n in self.sizes)
-        rows, cap = int(lib.vlsa_ilra_pool_part_rows()), int(lib.vlsa_ilra_pool_parts(1 << 62))
-        n = self.desc[:, 1]
-        self.part_start = torch.zeros(self.B + 1, dtype=torch.int32, device=n.device)
-        self.part_start[1:] = torch.cumsum(torch.clamp(torch.div(n + (rows - 1), rows, rounding_mode="floor"), 1, cap), 0)
+        self.part_table(lib.vlsa_ilra_pool_part_rows, lib.vlsa_ilra_pool_parts)
         self.ts, self.n_tiles = self.tables.tile_start(int(lib.vlsa_ilra_tile_rows()))
 
 
