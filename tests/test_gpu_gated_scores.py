@@ -212,3 +212,54 @@ def test_scores_pooling_and_adapter_head_other_widths_and_large_bags(R):
         assert (logit.double().reshape(-1) - want).abs().max().item() < 2e-5
 
 
+
+
+# ---- the batched entry point (vlsa_gated_scores_batch) below module level ----------------------------------------------------------
+# Both entry points pick their k_gated_scores instantiation in one dispatcher; the module route only ever asks the batched one for the
+# tile height score_tile_rows chooses.  Here it is called directly at both heights the dispatcher distinguishes.
+_BATCH_CASES = {}
+
+
+def _batch_case(sizes, gated, dtype):
+    """bags, weights and the oracle's scores per bag: made once per (sizes, module, dtype), shared by the tile heights"""
+    key = (sizes, gated, dtype)
+    if key not in _BATCH_CASES:
+        bags = [cases.make_bag(n, 3300 + 7 * i + n, "clustered" if i % 2 else "iid").to(dtype) for i, n in enumerate(sizes)]
+        W = _weights(3400 + sum(sizes), gated, scale=3.0)
+        _BATCH_CASES[key] = (bags, W, [_ref(x, *W) for x in bags])
+    return _BATCH_CASES[key]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("gated", [True, False])
+@pytest.mark.parametrize("shape", ["three_bags_rpt16", "three_bags_full", "one_bag_33_rows"])
+def test_batched_scores_vs_torch(shape, gated, dtype):
+    """max_rows + 1, 1 and 17 rows: a bag that crosses a tile edge and leaves a one-row tile, a one-row bag, a bag one row past a
+    16-row tile.  rows_per_tile = 16 takes the kernels that read the tile height at run time, rows_per_tile = max_rows of
+    vlsa_gated_scores_tiling (64 or 128) the static ones.  Reference and tolerance: those of test_fused_scores_vs_torch."""
+    from vlsa_amd import _native as nat
+    from vlsa_amd import functional as F
+    dev = torch.device("cuda", 0)
+    lib = nat.load()
+    max_rows, _ = F._score_tiling(dtype == torch.float32, gated)
+    assert max_rows in (64, 128)
+    sizes = (33,) if shape == "one_bag_33_rows" else (max_rows + 1, 1, 17)
+    rpt = max_rows if shape == "three_bags_full" else 16
+    bags, W, refs = _batch_case(sizes, gated, dtype)
+    Wd = [None if t is None else t.to(dev) for t in W]
+    prep = F.FusedAttnScores()._packed(dev, *Wd)
+    xs = [x.to(dev) for x in bags]
+    t = F.ChunkTables.from_host(F.bag_rows(xs), F._dt(xs[0]), rpt, dev, "test_batched_scores_vs_torch")
+    ts, n_tiles = t.p_tile_start(rpt)
+    assert n_tiles == sum((n + rpt - 1) // rpt for n in sizes)
+    a = torch.full((t.total,), float("nan"), dtype=torch.float32, device=dev)          # (the launch zeroes and fills every score)
+    nat.check(lib.vlsa_gated_scores_batch(t.p_desc, len(xs), F._dt(xs[0]), 512, F._p(prep), int(gated), ts, n_tiles, rpt, F._p(a),
+                                          t.p_row_off, t.total, F._stream()), "vlsa_gated_scores_batch")
+    torch.cuda.synchronize()
+    got = a.cpu()
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + n)
+    assert t.total == offs[-1]
+    for b, ref in enumerate(refs):
+        assert (got[offs[b]:offs[b + 1]] - ref).abs().max().item() < TOL, (b, sizes[b])

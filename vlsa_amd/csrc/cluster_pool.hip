@@ -27,6 +27,7 @@
 // to 1e-4) once per workgroup and issues 2 (bf16 rows) or 3 (fp32 rows as hi + lo: hi hi, hi lo, lo hi) MFMAs per fragment pair.
 // The R <= 64 partials ([256, 512] + [256] floats each: at most 32.1 MiB) are added in split order by k_cp_reduce: bit-reproducible.
 #include "bag_table.h"
+#include "launch.h"
 
 namespace {
 using namespace vlsa;
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(kThreads) void k_cp_reduce(int R, const float* __re
 }
 
 int check_common(const void* bag_desc, int B, int x_dtype, int D, int H, int Kc, const int* table, int n_table) {
-    if (!bag_desc || !table || B < 1 || B > 64 || n_table < B || Kc < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, table, n_table) || Kc < 1) return VLSA_EINVAL;
     if (D != kD || H != kH || Kc > kMaxK || (x_dtype != VLSA_DT_F32 && x_dtype != VLSA_DT_BF16)) return VLSA_EUNSUPPORTED;
     return VLSA_OK;
 }
@@ -463,7 +464,7 @@ extern "C" int vlsa_cluster_pool_forward_batch(const void* bag_desc, int B, int 
                            pcnt, mask);
     }
     hipLaunchKernelGGL(k_cp_merge, dim3(B * Kc), dim3(kThreads), 0, st, Kc, part_start, pS, pcnt, hc, cnt);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_cluster_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int Kc, const int* tile_start,
@@ -479,16 +480,12 @@ extern "C" int vlsa_cluster_pool_backward_batch(const void* bag_desc, int B, int
     float* pdb = pdW + (size_t)R * kH * kD;
     const long long* roff = reinterpret_cast<const long long*>(row_off);
     if (x_dtype == VLSA_DT_BF16) {
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)k_cp_backward<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdTile<__bf16>::kBytes);
-        hipLaunchKernelGGL(k_cp_backward<__bf16>, dim3(R, 4), dim3(kThreads), BwdTile<__bf16>::kBytes, st, bags, B, Kc, tile_start, n_tiles, roff,
-                           ids, mask, dhc, cnt, pdW, pdb);
+        launch_lds<k_cp_backward<__bf16>>(dim3(R, 4), dim3(kThreads), BwdTile<__bf16>::kBytes, st, bags, B, Kc, tile_start, n_tiles, roff,
+                                          ids, mask, dhc, cnt, pdW, pdb);
     } else {
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)k_cp_backward<float>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdTile<float>::kBytes);
-        hipLaunchKernelGGL(k_cp_backward<float>, dim3(R, 4), dim3(kThreads), BwdTile<float>::kBytes, st, bags, B, Kc, tile_start, n_tiles, roff, ids,
-                           mask, dhc, cnt, pdW, pdb);
+        launch_lds<k_cp_backward<float>>(dim3(R, 4), dim3(kThreads), BwdTile<float>::kBytes, st, bags, B, Kc, tile_start, n_tiles, roff, ids,
+                                         mask, dhc, cnt, pdW, pdb);
     }
     hipLaunchKernelGGL(k_cp_reduce, dim3(513), dim3(kThreads), 0, st, R, pdW, pdb, dWp, dbp);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

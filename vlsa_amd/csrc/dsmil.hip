@@ -21,6 +21,7 @@
 // classes) and leaves class (j * CP / 16) in lane j.  The weighted sums run as a register-tiled [CP x rows] x [rows x 512] product
 // out of an LDS copy of the row tile.
 #include "bag_table.h"
+#include "launch.h"
 
 namespace {
 using namespace vlsa;
@@ -299,8 +300,8 @@ __device__ __forceinline__ void write_weighted(float* scratch, const float (&acc
 // pass 2: per part (m, l, sum_n exp2(s - m) drop(x_n)) with the C rows of u as queries
 template <typename T, int CP, bool DROP>
 __global__ __launch_bounds__(kThreads) void k_dsmil_aggregate(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
-                                                              float drop_p, const long long* seed_word, float* pm, float* pl,
-                                                              float* pacc) {
+                                                              unsigned int drop_thr, float drop_scale, const long long* seed_word,
+                                                              float* pm, float* pl, float* pacc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ld = TileRow<T>::kLd;
     float* U = reinterpret_cast<float*>(lds);
@@ -322,8 +323,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_aggregate(const vlsa_bag_des
     float keep_scale = 1.f;
     if (DROP) {
         seed = bag_drop_seed((unsigned int)(*seed_word), b);
-        thr = (unsigned int)((double)drop_p * 4294967296.0);
-        keep_scale = 1.f / (1.f - drop_p);
+        thr = drop_thr;           // (drop_spec, launch.h: the backward recomputes the forward's mask from the same two numbers)
+        keep_scale = drop_scale;
     }
     float acc[CP][4];
 #pragma unroll
@@ -510,7 +511,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_bwd_prep(int C, const float*
 template <typename T, int CP, bool DROP>
 __global__ __launch_bounds__(kThreads) void k_dsmil_bwd_stream(const vlsa_bag_desc* bags, int B, int C, const int* part_start, const float* u,
                                                                const float* dz, const float* zdz, const float* m2, const float* l,
-                                                               float drop_p, const long long* seed_word, float* pdu) {
+                                                               unsigned int drop_thr, float drop_scale, const long long* seed_word,
+                                                               float* pdu) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int ld = TileRow<T>::kLd;
     float* U = reinterpret_cast<float*>(lds);
@@ -536,8 +538,8 @@ __global__ __launch_bounds__(kThreads) void k_dsmil_bwd_stream(const vlsa_bag_de
     float keep_scale = 1.f;
     if (DROP) {
         seed = bag_drop_seed((unsigned int)(*seed_word), b);
-        thr = (unsigned int)((double)drop_p * 4294967296.0);
-        keep_scale = 1.f / (1.f - drop_p);
+        thr = drop_thr;           // (drop_spec, launch.h: the backward recomputes the forward's mask from the same two numbers)
+        keep_scale = drop_scale;
     }
     float acc[CP][4];
 #pragma unroll
@@ -699,14 +701,9 @@ struct WsLayout {      // in floats
     }
 };
 
-template <typename K>
-void allow_lds(K kern, int bytes, DeviceOnce& once) {
-    if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 int check_common(const void* bag_desc, int B, int x_dtype, int D, int H, int C, const int* part_start, int n_parts, float drop_p,
-                 const int64_t* seed_word) {
-    if (!bag_desc || !part_start || B < 1 || B > 64 || n_parts < B || C < 1 || !(drop_p >= 0.f && drop_p < 1.f)) return VLSA_EINVAL;
+                 const int64_t* seed_word, DropSpec* drop) {
+    if (!bag_table_ok(bag_desc, B, part_start, n_parts) || C < 1 || !(drop_p >= 0.f) || !drop_spec(drop_p, drop)) return VLSA_EINVAL;
     if (drop_p > 0.f && !seed_word) return VLSA_EINVAL;
     if (D != kD || H != kH || C > kMaxC || (x_dtype != VLSA_DT_F32 && x_dtype != VLSA_DT_BF16)) return VLSA_EUNSUPPORTED;
     return VLSA_OK;
@@ -747,7 +744,8 @@ extern "C" int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype
                                         const float* Wv, const float* bv, const float* Wf, const float* bf, float drop_p,
                                         const int64_t* seed_word, void* ws, float* state, float* logits, float* attn,
                                         const int64_t* a_off, void* stream) {
-    const int rc = check_common(bag_desc, B, x_dtype, D, H, C, part_start, n_parts, drop_p, seed_word);
+    DropSpec ds;
+    const int rc = check_common(bag_desc, B, x_dtype, D, H, C, part_start, n_parts, drop_p, seed_word, &ds);
     if (rc != VLSA_OK) return rc;
     if (!Wc || !bc || !Wq || !bq || !Wv || !bv || !Wf || !bf || !ws || !state || !logits || (attn && !a_off)) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -762,7 +760,7 @@ extern "C" int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype
     float *u = state + s.u, *z = state + s.z, *bm = state + s.bm;
     const long long* seed = reinterpret_cast<const long long*>(seed_word);
     const long long* aoff = reinterpret_cast<const long long*>(a_off);
-    const bool f32 = x_dtype == VLSA_DT_F32, drop = drop_p > 0.f;
+    const bool f32 = x_dtype == VLSA_DT_F32, drop = ds.thr != 0u;
 
 #define DSMIL_SCORES(CP_)                                                                                                          \
     do {                                                                                                                           \
@@ -780,11 +778,8 @@ extern "C" int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype
 
 #define DSMIL_AGG_ONE(T_, CP_, DROP_)                                                                                              \
     do {                                                                                                                           \
-        auto kern = k_dsmil_aggregate<T_, CP_, DROP_>;                                                                             \
-        constexpr int bytes = tile_lds_bytes<T_, CP_, false>();                                                                    \
-        static DeviceOnce once;                                                                                                    \
-        allow_lds(kern, bytes, once);                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(n_parts), dim3(kThreads), bytes, st, bags, B, C, part_start, u, drop_p, seed, pm, pl, pacc);  \
+        launch_lds<k_dsmil_aggregate<T_, CP_, DROP_>>(dim3(n_parts), dim3(kThreads), tile_lds_bytes<T_, CP_, false>(), st, bags, B, C, \
+                                                      part_start, u, ds.thr, ds.scale, seed, pm, pl, pacc);                        \
     } while (0)
 #define DSMIL_AGG(CP_)                                  \
     do {                                                \
@@ -810,14 +805,15 @@ extern "C" int vlsa_dsmil_forward_batch(const void* bag_desc, int B, int x_dtype
         DSMIL_BY_CP(DSMIL_ATTN);
 #undef DSMIL_ATTN
     }
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, int C, const int* part_start,
                                          int n_parts, const float* Wq, const float* Wv, const float* Wf, const float* dlogits,
                                          float drop_p, const int64_t* seed_word, const float* state, void* ws, float* dWc, float* dbc,
                                          float* dWq, float* dbq, float* dWv, float* dbv, float* dWf, float* dbf, void* stream) {
-    const int rc = check_common(bag_desc, B, x_dtype, D, H, C, part_start, n_parts, drop_p, seed_word);
+    DropSpec ds;
+    const int rc = check_common(bag_desc, B, x_dtype, D, H, C, part_start, n_parts, drop_p, seed_word, &ds);
     if (rc != VLSA_OK) return rc;
     if (!Wq || !Wv || !Wf || !dlogits || !state || !ws || !dWc || !dbc || !dWq || !dbq || !dWv || !dbv || !dWf || !dbf) return VLSA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -829,17 +825,13 @@ extern "C" int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtyp
     const float *m2 = state + s.m2, *l = state + s.l, *xcrit = state + s.xcrit, *qmax = state + s.qmax, *u = state + s.u;
     const float *z = state + s.z, *bm = state + s.bm;
     const long long* seed = reinterpret_cast<const long long*>(seed_word);
-    const bool f32 = x_dtype == VLSA_DT_F32, drop = drop_p > 0.f;
+    const bool f32 = x_dtype == VLSA_DT_F32, drop = ds.thr != 0u;
 
     hipLaunchKernelGGL(k_dsmil_bwd_prep, dim3(B * C), dim3(kThreads), 0, st, C, Wv, Wf, dlogits, z, dB, dz, zdz);
 #define DSMIL_BWD_ONE(T_, CP_, DROP_)                                                                                              \
     do {                                                                                                                           \
-        auto kern = k_dsmil_bwd_stream<T_, CP_, DROP_>;                                                                            \
-        constexpr int bytes = tile_lds_bytes<T_, CP_, true>();                                                                     \
-        static DeviceOnce once;                                                                                                    \
-        allow_lds(kern, bytes, once);                                                                                              \
-        hipLaunchKernelGGL(kern, dim3(n_parts), dim3(kThreads), bytes, st, bags, B, C, part_start, u, dz, zdz, m2, l, drop_p, seed, \
-                           pdu);                                                                                                   \
+        launch_lds<k_dsmil_bwd_stream<T_, CP_, DROP_>>(dim3(n_parts), dim3(kThreads), tile_lds_bytes<T_, CP_, true>(), st, bags, B, C, \
+                                                       part_start, u, dz, zdz, m2, l, ds.thr, ds.scale, seed, pdu);                \
     } while (0)
 #define DSMIL_BWD(CP_)                                  \
     do {                                                \
@@ -854,5 +846,5 @@ extern "C" int vlsa_dsmil_backward_batch(const void* bag_desc, int B, int x_dtyp
     hipLaunchKernelGGL(k_dsmil_bwd_merge, dim3(B * C), dim3(kThreads), 0, st, C, part_start, pdu, Wq, du, dqm);
     hipLaunchKernelGGL(k_dsmil_bwd_params, dim3(513 + C), dim3(kThreads), 0, st, B, C, dlogits, xcrit, qmax, z, bm, dB, du, dqm, dWc,
                        dbc, dWq, dbq, dWv, dbv, dWf, dbf);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

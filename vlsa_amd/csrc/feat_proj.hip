@@ -18,6 +18,7 @@
 // Roofline: MFMA-bound, 2 terms x 2 x 512 x 512 = 1.05 MFLOP per patch (the same as the gated attention scores) plus 2 KB
 // per patch written.
 #include "feat_proj.h"
+#include "launch.h"
 
 #ifndef FP_XBUF
 #define FP_XBUF 1
@@ -297,7 +298,7 @@ extern "C" int vlsa_prepare_featproj(const float* W, const float* b, const float
     if (dim_in != fp::kD || dim_out != fp::kD) return VLSA_EUNSUPPORTED;
     hipLaunchKernelGGL(k_prepare_featproj, dim3(8 * fp::kSteps * fp::kNF), dim3(64), 0, (hipStream_t)stream, W, b, gamma, beta,
                        static_cast<unsigned char*>(prep));
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // rows per workgroup for a launch over N rows: every workgroup streams the whole 1 MB of packed weights from L2, so the largest tile
@@ -330,7 +331,7 @@ static int feat_project_impl(const void* X, int x_dtype, int64_t N, int64_t ldx,
         else VLSA_FP(false, 2);
     }
 #undef VLSA_FP
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_feat_project(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const void* prep, float eps, float* Y,
@@ -360,7 +361,7 @@ extern "C" int vlsa_feat_project_batch_tile_rows(int x_dtype, int64_t total_rows
 // as by vlsa_feat_project_train.  Every row equals, bit for bit, what the single-bag entry points give for it.
 extern "C" int vlsa_feat_project_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, float eps, const int* tile_start,
                                        int n_tiles, int tile_rows, float* Y, const int64_t* row_off, float* stats, void* stream) {
-    if (!bag_desc || !prep || !tile_start || !Y || !row_off || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !prep || !Y || !row_off) return VLSA_EINVAL;
     if (D != fp::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     const bool f32 = x_dtype == VLSA_DT_F32;
     if (tile_rows != 32 && tile_rows != 64 && !(tile_rows == 128 && !f32)) return VLSA_EINVAL;
@@ -380,5 +381,5 @@ extern "C" int vlsa_feat_project_batch(const void* bag_desc, int B, int x_dtype,
         else VLSA_FPB(false, 2);
     }
 #undef VLSA_FPB
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

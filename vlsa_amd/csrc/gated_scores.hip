@@ -42,6 +42,7 @@
 
 #include "vlsa_common.h"
 #include "gated_scores.h"
+#include "launch.h"
 
 // Timing-only ablations of k_gated_scores (results are WRONG with any bit set; tools/attic/gs_ablate.sh builds one library per bit):
 // 1 = no A-fragment reads from LDS, 2 = no weight loads, 4 = no X loads / publication, 8 = no per-step barrier,
@@ -431,7 +432,7 @@ extern "C" int vlsa_prepare_gated_weights(const float* Wa, const float* ba, cons
     const int NF = gated ? 4 : 2;
     hipLaunchKernelGGL(k_prepare_gated_weights, dim3(gs::kHalves * 8 * gs::kSteps * NF), dim3(64), 0, (hipStream_t)stream, Wa, ba, Wg, bg, w2, c,
                        gated ? 1 : 0, static_cast<unsigned char*>(prep));
-    if (hipGetLastError() != hipSuccess) return VLSA_ELAUNCH;
+    if (launch_status() != VLSA_OK) return VLSA_ELAUNCH;
     return gs_tile_prepare(Wa, Wg, gated, static_cast<unsigned char*>(prep), (hipStream_t)stream);
 }
 
@@ -532,6 +533,43 @@ extern "C" int vlsa_gated_scores_tiling(int x_dtype, int gated, int* max_rows, i
     return VLSA_OK;
 }
 
+// The one place that maps (tiling, bag dtype, module, whole tiles) to an instantiation of k_gated_scores and launches it: the single-bag
+// segments and the batched launch differ in the arguments they built (X / N / ldx or a bag table in `bt`), not in the kernel.
+// tiles = row tiles x tl.halves.  full: rows_per_tile is the shape's max_rows (the kernel's static tile height), otherwise the kernel
+// takes the height at run time.  LDS: the images of the four-wave shapes fit gs::kLds for either dtype, the 8-wave fp32 shapes need
+// gs::kLds32.  (The arms stand in the order the kernels have always been instantiated in, which is their order in the code object.)
+struct GsCall {
+    unsigned int tiles;
+    hipStream_t st;
+    const void* X;
+    long long N, ldx;
+    const unsigned char* prep;
+    float* a;
+    int rows_per_tile;
+    GsBatch bt;
+};
+template <bool GATED, bool FULL, bool XF32, int RT, int HG, int NW>
+static void gs_go(const GsCall& c) {
+    launch_lds<k_gated_scores<GATED, FULL, XF32, RT, HG, NW>>(dim3(c.tiles), dim3(64 * NW), XF32 && NW == 8 ? gs::kLds32 : gs::kLds, c.st, c.X,
+                                                               c.N, c.ldx, c.prep, c.a, c.rows_per_tile, c.bt);
+}
+static void gs_launch(const GsTiling& tl, bool f32, bool gated, bool full, const GsCall& c) {
+#define VLSA_GS(G, X32, RT, HG, NW) do { if (full) gs_go<G, true, X32, RT, HG, NW>(c); else gs_go<G, false, X32, RT, HG, NW>(c); } while (0)
+    if (!tl.four_waves) {       // the 8-wave shapes of rounds 1-2: behind the VLSA_GS_G4 / VLSA_GS_F4 / VLSA_GS_HG2 hooks (-DVLSA_EXPERIMENT) only
+        if (!f32) { if (gated) VLSA_GS(true, false, 16, 1, 8); else VLSA_GS(false, false, 16, 1, 8); }
+        else      { if (gated) VLSA_GS(true, true, 8, 1, 8); else VLSA_GS(false, true, 16, 1, 8); }
+    } else if (f32) {
+        if (gated) VLSA_GS(true, true, 4, 2, 4); else VLSA_GS(false, true, 8, 2, 4);
+    } else if (gated) {
+        VLSA_GS(true, false, 4, 2, 4);
+    } else if (tl.halves == 1) {
+        gs_go<false, false, false, 8, 4, 4>(c);      // all 256 hidden units per workgroup: run-time tile height only
+    } else {
+        VLSA_GS(false, false, 8, 2, 4);
+    }
+#undef VLSA_GS
+}
+
 static int gated_scores_impl(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const void* prep, int gated, float* a,
                              float drop_p, unsigned int seed, void* stream) {
     if (!X || !prep || !a || N < 1 || ldx < D) return VLSA_EINVAL;
@@ -539,17 +577,6 @@ static int gated_scores_impl(const void* X, int x_dtype, int64_t N, int64_t ldx,
     const bool f32 = x_dtype == VLSA_DT_F32;
     const long long esz = f32 ? 4 : 2;
     if ((reinterpret_cast<uintptr_t>(X) & 15) || ((ldx * esz) % 16) || ldx * esz * gs::kRows >= (1ll << 31)) return VLSA_EINVAL;
-    static DeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, true, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-    }
     // Rows per tile.  One round of the 256 CUs covers 2 halves x 128 tiles.  A bag that fits one round (N <= 128 tiles of the
     // largest height) uses the smallest multiple of 16 rows that still fits it (a 2 798-patch bag runs as 2 x 88 tiles of 32
     // rows instead of 2 x 11 of 256).  A larger bag is covered by TWO launches: whole rounds of the static 256-row kernel
@@ -562,11 +589,11 @@ static int gated_scores_impl(const void* X, int x_dtype, int64_t N, int64_t ldx,
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
     GsBatch dropb{nullptr, nullptr, nullptr, 0, 0u, 0u, 1.f, 0u};
     if (gated && drop_p > 0.f) {
-        if (!(drop_p < 1.f)) return VLSA_EINVAL;
-        dropb.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
-        if (dropb.drop_thr == 0u) dropb.drop_thr = 1u;
+        DropSpec ds;
+        if (!drop_spec(drop_p, &ds)) return VLSA_EINVAL;
+        dropb.drop_thr = ds.thr;
         dropb.drop_seed = seed;
-        dropb.drop_scale = 1.f / (1.f - drop_p);
+        dropb.drop_scale = ds.scale;
     }
     // round 5: large bf16 bags take the LDS-DMA tile kernel (gated_scores_tile.hip)
     if (!f32 && gs_tile_use(gated != 0, (long long)N) && 256ll * ldx * 2 < (1ll << 31)) {
@@ -605,37 +632,10 @@ static int gated_scores_impl(const void* X, int x_dtype, int64_t N, int64_t ldx,
         const void* Xs = static_cast<const unsigned char*>(X) + off * ldx * esz;
         float* as = a + off;
         dropb.row_base = (unsigned int)off;
-#define VLSA_GS(G, F, X32) hipLaunchKernelGGL((k_gated_scores<G, F, X32>), dim3(tiles), dim3(512), X32 ? gs::kLds32 : gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb)
-#define VLSA_GS2(F) hipLaunchKernelGGL((k_gated_scores<false, F, false, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb)
-#define VLSA_GS3(F) hipLaunchKernelGGL((k_gated_scores<false, F, false, 8, 4, 4>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb)
-        if (f32 && gated && tl.four_waves) {
-            if (full) hipLaunchKernelGGL((k_gated_scores<true, true, true, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-            else hipLaunchKernelGGL((k_gated_scores<true, false, true, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-        } else if (f32 && tl.four_waves) {
-            if (full) hipLaunchKernelGGL((k_gated_scores<false, true, true, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-            else hipLaunchKernelGGL((k_gated_scores<false, false, true, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-        } else if (gated && tl.four_waves) {
-            if (full) hipLaunchKernelGGL((k_gated_scores<true, true, false, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-            else hipLaunchKernelGGL((k_gated_scores<true, false, false, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-        } else if (tl.four_waves && tl.halves == 1) {
-            VLSA_GS3(false);
-        } else if (tl.four_waves) {
-            if (full) VLSA_GS2(true); else VLSA_GS2(false);
-        } else if (f32) {
-            if (gated) {
-                if (full) hipLaunchKernelGGL((k_gated_scores<true, true, true, 8>), dim3(tiles), dim3(512), gs::kLds32, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-                else hipLaunchKernelGGL((k_gated_scores<true, false, true, 8>), dim3(tiles), dim3(512), gs::kLds32, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb);
-            } else { if (full) VLSA_GS(false, true, true); else VLSA_GS(false, false, true); }
-        } else {
-            if (gated) { if (full) VLSA_GS(true, true, false); else VLSA_GS(true, false, false); }
-            else       { if (full) VLSA_GS(false, true, false); else VLSA_GS(false, false, false); }
-        }
-#undef VLSA_GS
-#undef VLSA_GS2
-#undef VLSA_GS3
+        gs_launch(tl, f32, gated != 0, full, GsCall{tiles, st, Xs, (long long)n, (long long)ldx, pp, as, rows_per_tile, dropb});
         off += n;
     }
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_gated_scores(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const void* prep, int gated, float* a,
@@ -657,14 +657,14 @@ extern "C" int vlsa_gated_scores_train(const void* X, int x_dtype, int64_t N, in
 static int gated_scores_batch_impl(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
                                    const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
                                    int64_t a_floats, float drop_p, const int64_t* seed_word, void* stream) {
-    if (!bag_desc || !prep || !a || !tile_start || !a_off || B < 1 || B > 64 || n_tiles < 1 || a_floats < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !prep || !a || !a_off || a_floats < 1) return VLSA_EINVAL;
     if (D != gs::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     GsBatch bt{static_cast<const vlsa_bag_desc*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u, nullptr};
-    if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_train; the seed comes from the device word
-        if (!(drop_p < 1.f) || !seed_word) return VLSA_EINVAL;
-        bt.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
-        if (bt.drop_thr == 0u) bt.drop_thr = 1u;
-        bt.drop_scale = 1.f / (1.f - drop_p);
+    if (gated && drop_p > 0.f) {     // the seed comes from the device word
+        DropSpec ds;
+        if (!drop_spec(drop_p, &ds) || !seed_word) return VLSA_EINVAL;
+        bt.drop_thr = ds.thr;
+        bt.drop_scale = ds.scale;
         bt.seed_word = reinterpret_cast<const long long*>(seed_word);
     }
     const bool f32 = x_dtype == VLSA_DT_F32;
@@ -677,46 +677,11 @@ static int gated_scores_batch_impl(const void* bag_desc, int B, int x_dtype, int
         return gs_tile_launch(nullptr, 0ll, 0ll, static_cast<const unsigned char*>(prep), gated, a, n_tiles, rows_per_tile, bt, nullptr, nullptr, st);
     }
     if (rows_per_tile < 16 || rows_per_tile > max_rows || (rows_per_tile % 16)) return VLSA_EINVAL;
-    static DeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, true, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<true, false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-        (void)hipFuncSetAttribute((const void*)k_gated_scores<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gs::kLds32);
-    }
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(a, 0, (size_t)a_floats * sizeof(float), st) != hipSuccess) return VLSA_ELAUNCH;
-    const bool full = rows_per_tile == max_rows;
-    const unsigned int tiles = (unsigned int)n_tiles * tl.halves;
-    const unsigned char* pp = static_cast<const unsigned char*>(prep);
-#define VLSA_GSB(G, F, X32, RTV) hipLaunchKernelGGL((k_gated_scores<G, F, X32, RTV>), dim3(tiles), dim3(512), X32 ? gs::kLds32 : gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt)
-    if (f32 && gated && tl.four_waves) {
-        if (full) hipLaunchKernelGGL((k_gated_scores<true, true, true, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-        else hipLaunchKernelGGL((k_gated_scores<true, false, true, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-    } else if (f32 && tl.four_waves) {
-        if (full) hipLaunchKernelGGL((k_gated_scores<false, true, true, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-        else hipLaunchKernelGGL((k_gated_scores<false, false, true, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-    } else if (gated && tl.four_waves) {
-        if (full) hipLaunchKernelGGL((k_gated_scores<true, true, false, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-        else hipLaunchKernelGGL((k_gated_scores<true, false, false, 4, 2, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-    } else if (tl.four_waves && tl.halves == 1) {
-        hipLaunchKernelGGL((k_gated_scores<false, false, false, 8, 4, 4>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-    } else if (tl.four_waves) {
-        if (full) hipLaunchKernelGGL((k_gated_scores<false, true, false, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-        else hipLaunchKernelGGL((k_gated_scores<false, false, false, 8, 2>), dim3(tiles), dim3(256), gs::kLds, st, (const void*)nullptr, 0ll, 0ll, pp, a, rows_per_tile, bt);
-    } else if (f32) {
-        if (gated) { if (full) VLSA_GSB(true, true, true, 8); else VLSA_GSB(true, false, true, 8); }
-        else       { if (full) VLSA_GSB(false, true, true, 16); else VLSA_GSB(false, false, true, 16); }
-    } else {
-        if (gated) { if (full) VLSA_GSB(true, true, false, 16); else VLSA_GSB(true, false, false, 16); }
-        else       { if (full) VLSA_GSB(false, true, false, 16); else VLSA_GSB(false, false, false, 16); }
-    }
-#undef VLSA_GSB
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    gs_launch(tl, f32, gated != 0, rows_per_tile == max_rows,
+              GsCall{(unsigned int)n_tiles * tl.halves, st, nullptr, 0ll, 0ll, static_cast<const unsigned char*>(prep), a, rows_per_tile, bt});
+    return launch_status();
 }
 
 extern "C" int vlsa_gated_scores_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
@@ -746,7 +711,7 @@ extern "C" int vlsa_gated_scores_batch_train(const void* bag_desc, int B, int x_
 extern "C" int vlsa_gated_scores_pool_batch(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
                                             const int* tile_start, int n_tiles, int rows_per_tile, float* a, const int64_t* a_off,
                                             float* ws, float* pooled, void* stream) {
-    if (!bag_desc || !prep || !a || !tile_start || !a_off || !ws || !pooled || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !prep || !a || !a_off || !ws || !pooled) return VLSA_EINVAL;
     if (D != gs::kD || x_dtype != VLSA_DT_BF16) return VLSA_EUNSUPPORTED;
     const GsBatch bt{static_cast<const vlsa_bag_desc*>(bag_desc), tile_start, reinterpret_cast<const long long*>(a_off), B, 0u, 0u, 1.f, 0u};
     return gs_tile_launch(nullptr, 0ll, 0ll, static_cast<const unsigned char*>(prep), gated, a, n_tiles, rows_per_tile, bt, ws, pooled,

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "gated_scores.h"
+#include "launch.h"
 
 // Timing-only ablations (results are WRONG with any bit set; tools/gt_ablate.py builds one library per value): 16 = no activations,
 // 32 = no MFMAs (the operands still arrive in registers).  (The one-tile-per-workgroup versions of this kernel had more: no weight /
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(512) void k_pool_fold_tiles(const float* __restrict
 int gs_tile_prepare(const float* Wa, const float* Wg, int gated, unsigned char* prep, hipStream_t st) {
     const int chunks = (gated ? 2 : 1) * gs::kSteps * 2 * 256 * 4;
     hipLaunchKernelGGL(k_prepare_tile_weights, dim3(chunks / 256), dim3(256), 0, st, Wa, Wg, gated ? 1 : 0, prep);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // Tiling of a single-bag launch: U = ceil(N / (16 walkers)) 16-row units per walker in R = ceil(U / 16) rounds (a round = one tile per
@@ -579,13 +580,6 @@ int gs_tile_pool_tiles(long long N) { return gs_tile_plan(N, 256).n_tiles; }
 
 int gs_tile_launch(const void* X, long long N, long long ldx, const unsigned char* prep, int gated, float* a, int n_tiles,
                    int rows_per_tile, const GsBatch& bt, float* ws, float* pooled, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_scores_tile_p<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gt::kLdsP);
-        (void)hipFuncSetAttribute((const void*)k_scores_tile_p<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gt::kLdsP);
-        (void)hipFuncSetAttribute((const void*)k_scores_tile_p<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gt::kLdsP);
-        (void)hipFuncSetAttribute((const void*)k_scores_tile_p<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gt::kLdsP);
-    }
     const bool pool = ws != nullptr;
     if (pool && pooled == nullptr) return VLSA_EINVAL;
     const int walkers = (gated && !pool) ? 128 : 256;       // (pooling: a workgroup walks both column halves of its row tiles)
@@ -602,17 +596,15 @@ int gs_tile_launch(const void* X, long long N, long long ldx, const unsigned cha
     const int wg = n_tiles < walkers ? n_tiles : walkers;
     const unsigned int grid = (gated && !pool) ? 2u * (unsigned)((wg + 7) / 8 * 8) : (unsigned)wg;
     const GtPool gp{ws, ws ? ws + n_tiles : nullptr, ws ? ws + 2ll * n_tiles : nullptr};
-#define VLSA_GTP(G, P) hipLaunchKernelGGL((k_scores_tile_p<G, P>), dim3(grid), dim3(512), gt::kLdsP, st, X, N, ldx, prep, a, n_tiles, nrt, tall_rounds, bt, gp)
-    if (gated) { if (pool) VLSA_GTP(true, true); else VLSA_GTP(true, false); }
-    else       { if (pool) VLSA_GTP(false, true); else VLSA_GTP(false, false); }
+#define VLSA_GTP(G, P) launch_lds<k_scores_tile_p<G, P>>(dim3(grid), dim3(512), gt::kLdsP, st, X, N, ldx, prep, a, n_tiles, nrt, tall_rounds, bt, gp)
+    if (!pool) { if (gated) VLSA_GTP(true, false); else VLSA_GTP(false, false); }
+    else       { if (gated) VLSA_GTP(true, true); else VLSA_GTP(false, true); }
 #undef VLSA_GTP
-    if (hipGetLastError() != hipSuccess) return VLSA_ELAUNCH;
-    if (pool) {
-        hipLaunchKernelGGL(k_pool_fold_tiles, dim3(bt.bags ? bt.B : 1, 16), dim3(512), 0, st, gp.m, gp.l, gp.acc,
-                           bt.bags ? bt.tile_start : (const int*)nullptr, n_tiles, pooled);
-        if (hipGetLastError() != hipSuccess) return VLSA_ELAUNCH;
-    }
-    return VLSA_OK;
+    if (launch_status() != VLSA_OK) return VLSA_ELAUNCH;
+    if (!pool) return VLSA_OK;
+    hipLaunchKernelGGL(k_pool_fold_tiles, dim3(bt.bags ? bt.B : 1, 16), dim3(512), 0, st, gp.m, gp.l, gp.acc,
+                       bt.bags ? bt.tile_start : (const int*)nullptr, n_tiles, pooled);
+    return launch_status();
 }
 
 }  // namespace vlsa

@@ -23,6 +23,7 @@
 // workspace, forms du = do + Wo^T dt (and dX = Wq^T du + Wg^T ds for packed rows) in the same kernel, then three [256, n] x [n, D]
 // products (k_rm_wgrad: row splits in registers, partials added in split order) and the column sums per bag.
 #include "bag_table.h"
+#include "launch.h"
 
 namespace {
 using namespace vlsa;
@@ -589,7 +590,7 @@ __global__ __launch_bounds__(kThreads) void k_rm_colfold(int B, const float* __r
 
 // 0: bf16 bag rows, 1: fp32 bag rows (D = 512); 2: packed fp32 rows (D = 256); < 0: the error
 int source_of(const void* bag_desc, int B, int x_dtype, int D, const void* xp, const int* table, int n_table, const void* row_off) {
-    if (!bag_desc || !table || !row_off || B < 1 || B > 64 || n_table < B) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, table, n_table) || !row_off) return VLSA_EINVAL;
     if (x_dtype != VLSA_DT_F32 && x_dtype != VLSA_DT_BF16) return VLSA_EUNSUPPORTED;
     if (xp == nullptr) return D == 512 ? (x_dtype == VLSA_DT_BF16 ? 0 : 1) : VLSA_EUNSUPPORTED;
     return (D == 256 && x_dtype == VLSA_DT_F32) ? 2 : VLSA_EUNSUPPORTED;
@@ -638,7 +639,7 @@ extern "C" int vlsa_ilra_pool_forward_batch(const void* bag_desc, int B, int x_d
     else
         hipLaunchKernelGGL((k_ip_forward<float, 256>), dim3(n_parts), dim3(kThreads), 0, st, bags, B, P, part_start, roff, xp, E, pm, pl, pZ);
     hipLaunchKernelGGL(k_ip_merge, dim3(B, P), dim3(kThreads), 0, st, D, part_start, pm, pl, pZ, P, Z, m, l);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_ilra_pool_backward_batch(const void* bag_desc, int B, int x_dtype, int D, int P, const int* part_start, int n_parts,
@@ -666,7 +667,7 @@ extern "C" int vlsa_ilra_pool_backward_batch(const void* bag_desc, int B, int x_
         hipLaunchKernelGGL((k_ip_backward<float, 256, true>), dim3(n_parts), dim3(kThreads), 0, st, bags, B, P, part_start, roff, xp, E, dZ, Z, m,
                            l, pdE, dX);
     hipLaunchKernelGGL(k_ip_reduce, dim3((P * D + kThreads - 1) / kThreads), dim3(kThreads), 0, st, D, P, n_parts, pdE, dE);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_ilra_rowmap_forward_batch(const void* bag_desc, int B, int x_dtype, int D, int H, const int* tile_start, int n_tiles,
@@ -688,7 +689,7 @@ extern "C" int vlsa_ilra_rowmap_forward_batch(const void* bag_desc, int B, int x
     else
         hipLaunchKernelGGL((k_rm_forward<float, 256>), dim3(n_tiles), dim3(kThreads), 0, st, bags, B, tile_start, roff, xp, Wq, btil, Wo, bo, Wg,
                            bg, out, mask);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 namespace {
@@ -750,5 +751,5 @@ extern "C" int vlsa_ilra_rowmap_backward_batch(const void* bag_desc, int B, int 
 #undef VLSA_RM_BWD
     hipLaunchKernelGGL(k_rm_colsum, dim3(B, 3, kSegs), dim3(kThreads), 0, st, bags, roff, total, w, pcs);
     hipLaunchKernelGGL(k_rm_colfold, dim3(B + 1), dim3(kThreads), 0, st, B, pcs, dbtil, dbo, dbg);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

@@ -4,6 +4,7 @@
 // this kernel packs freshly copied rows into the resident arena: fp32 -> bf16 round-to-nearest-even (== torch's
 // .to(torch.bfloat16) for finite values and infinities), or a strided bf16 copy.  Pure streaming: 16-byte loads and stores.
 #include "vlsa_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -66,5 +67,5 @@ extern "C" int vlsa_pack_rows_bf16(const void* src, int src_dtype, int64_t N, in
                            D, static_cast<__bf16*>(dst), ldd);
     else
         return VLSA_EINVAL;
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

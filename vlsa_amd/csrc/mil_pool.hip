@@ -9,6 +9,7 @@
 // All of them are HBM-bound streaming reductions: one wave per patch row, 16-byte (bf16) / 8-byte loads per
 // lane are not needed here because a row is spread over the 64 lanes with unit stride (fully coalesced).
 #include "vlsa_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -900,7 +901,6 @@ __global__ __launch_bounds__(512) void k_zeroshot_backward(const vlsa_bag_desc* 
 
 using namespace vlsa;
 
-static inline int st() { return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH; }
 
 extern "C" int vlsa_pool_num_partials(int64_t N) {
     const int64_t t = (N + 63) / 64;
@@ -926,11 +926,11 @@ static int launch_scored(const XT* X, int64_t N, int64_t ldx, int D, const float
     }
         if (NC == 1) VLSA_SPV(1) else if (NC == 2) VLSA_SPV(2) else if (NC == 3) VLSA_SPV(3) else VLSA_SPV(4)
 #undef VLSA_SPV
-        return st();
+        return launch_status();
     }
     if (D <= 256) VLSA_SP(4) else if (D <= 512) VLSA_SP(8) else if (D <= 768) VLSA_SP(12) else VLSA_SP(16)
 #undef VLSA_SP
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_scored_pool_partial(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const float* scores,
@@ -961,7 +961,7 @@ extern "C" int vlsa_scored_pool_partial_batch(const void* bag_desc, int B, int x
         hipLaunchKernelGGL((k_scored_pool_partial_vec<__bf16, 1>), dim3(G, B), dim3(256), lds, s, static_cast<const __bf16*>(nullptr), (int64_t)0,
                            (int64_t)0, D, scores, pm, pl, pacc, G, bags, off);
     }
-    return st();
+    return launch_status();
 }
 
 template <typename XT>
@@ -984,7 +984,7 @@ static int launch_colmax(const XT* X, int64_t N, int64_t ldx, int D, float* part
     } else if (D <= 256) VLSA_CM(4) else if (D <= 512) VLSA_CM(8) else if (D <= 768) VLSA_CM(12) else VLSA_CM(16)
 #undef VLSA_CM
     hipLaunchKernelGGL(k_colmax_merge, dim3((D + 63) / 64), dim3(256), 0, s, part, G, D, out);
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_colmax(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, float* partials, float* out,
@@ -1002,7 +1002,7 @@ extern "C" int vlsa_attn_scores(const float* H, const float* Hg, int64_t N, int 
     int64_t nb = (N + 3) / 4;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_attn_scores, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, H, Hg, N, hid, b1, bg, w2, b2, a);
-    return st();
+    return launch_status();
 }
 
 // (Gated_)Attention_Pooling over the P aggregated rows of B bags (VLFAN query pooling): rows [B, P, D] -> pooled [B, D],
@@ -1018,7 +1018,7 @@ extern "C" int vlsa_query_pool_attention(const float* rows, int B, int P, int D,
     float* part = static_cast<float*>(workspace);
     hipLaunchKernelGGL(k_qpool_scores, dim3(nchunk, B), dim3(256), (size_t)P * D * sizeof(float), s, rows, P, D, Wa, ba, Wg, bg, w2, hid, part);
     hipLaunchKernelGGL(k_qpool_finish, dim3(B), dim3(256), 0, s, rows, P, D, part, nchunk, c, want_raw, pooled, scores);
-    return st();
+    return launch_status();
 }
 
 static int rowdot_impl(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const float* v, float* out, const float* a,
@@ -1037,14 +1037,14 @@ static int rowdot_impl(const void* X, int x_dtype, int64_t N, int64_t ldx, int D
         if (x_dtype == VLSA_DT_BF16) { if (NC == 1) VLSA_RD(__bf16, 1); else VLSA_RD(__bf16, 2); }
         else { if (NC == 1) VLSA_RD(float, 1); else if (NC == 2) VLSA_RD(float, 2); else if (NC == 3) VLSA_RD(float, 3); else VLSA_RD(float, 4); }
 #undef VLSA_RD
-        return st();
+        return launch_status();
     }
     if (a != nullptr) return VLSA_EUNSUPPORTED;
     if (x_dtype == VLSA_DT_F32)
         hipLaunchKernelGGL(k_rowdot<float>, dim3((unsigned)nb), dim3(256), 0, s, (const float*)X, N, ldx, D, v, out);
     else
         hipLaunchKernelGGL(k_rowdot<__bf16>, dim3((unsigned)nb), dim3(256), 0, s, (const __bf16*)X, N, ldx, D, v, out);
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_rowdot(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, const float* v, float* out,
@@ -1078,14 +1078,14 @@ extern "C" int vlsa_topk_mean_ws(const float* S, int C, int64_t N, int k, float 
     float* part = static_cast<float*>(workspace);
     if (G == 1 || ((int64_t)k < N && (int64_t)k * 2 > N / G)) {  // short rows: the single-stage kernel
         hipLaunchKernelGGL(k_topk_mean, dim3(C), dim3(256), 0, s, S, N, k, out_scale, out);
-        return st();
+        return launch_status();
     }
     hipLaunchKernelGGL(k_topk_partial, dim3(G, C), dim3(256), 0, s, S, N, k, G, part);
     if ((int64_t)k >= N)
         hipLaunchKernelGGL(k_mean_final, dim3(C), dim3(64), 0, s, part, G, N, out_scale, out);
     else
         hipLaunchKernelGGL(k_topk_mean, dim3(C), dim3(256), 0, s, part, (int64_t)G * k, k, out_scale, out);
-    return st();
+    return launch_status();
 }
 
 // The k largest entries of every row of S [C, N], descending, -inf padded when N < k: vals [C, k].  The per-rank piece of the
@@ -1098,11 +1098,11 @@ extern "C" int vlsa_topk_values(const float* S, int C, int64_t N, int k, void* w
     float* part = static_cast<float*>(workspace);
     if (G == 1) {
         hipLaunchKernelGGL(k_topk_partial, dim3(1, C), dim3(256), 0, s, S, N, k, 1, vals, 1);
-        return st();
+        return launch_status();
     }
     hipLaunchKernelGGL(k_topk_partial, dim3(G, C), dim3(256), 0, s, S, N, k, G, part, 1);
     hipLaunchKernelGGL(k_topk_partial, dim3(1, C), dim3(256), 0, s, part, (int64_t)G * k, k, 1, vals, 1);
-    return st();
+    return launch_status();
 }
 
 // Per-class top-k mean for B bags in one launch (model/deepmil.py:16-37 on the [C, N_i] class scores of every bag):
@@ -1114,7 +1114,7 @@ extern "C" int vlsa_topk_mean_batch(const void* bag_desc, const void* scores_des
     const int kk = k <= 0 ? 0x7fffffff : k;      // mean over all patches
     hipLaunchKernelGGL(k_topk_mean_batch<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, static_cast<const vlsa_bag_desc*>(bag_desc),
                        static_cast<const vlsa_rows_desc*>(scores_desc), C, kk, logit_scale, out, (int*)nullptr, 0);
-    return st();
+    return launch_status();
 }
 
 // The same launch for the differentiable zero-shot route: out is bit-equal to vlsa_topk_mean_batch's, and for 1 <= k <= 32
@@ -1131,7 +1131,7 @@ extern "C" int vlsa_topk_select_batch(const void* bag_desc, const void* scores_d
                            (int*)nullptr, 0);
     else
         hipLaunchKernelGGL(k_topk_mean_batch<true>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, bd, sd, C, k, logit_scale, out, idx, k);
-    return st();
+    return launch_status();
 }
 
 extern "C" size_t vlsa_unit_mean_workspace_bytes(int B) { return (size_t)(B < 1 ? 1 : B) * kUnitParts * 512 * sizeof(float); }
@@ -1150,7 +1150,7 @@ extern "C" int vlsa_unit_mean_batch(const void* bag_desc, int B, int x_dtype, in
     else
         hipLaunchKernelGGL(k_unit_mean_partial<float>, dim3(grid), dim3(256), 0, s, bd, B, part);
     hipLaunchKernelGGL(k_unit_mean_finish, dim3(B), dim3(256), 0, s, bd, part, u);
-    return st();
+    return launch_status();
 }
 
 // dT [C, 512] and d logit_scale [1] (nullable) of the zero-shot bag logits [B, C] in ONE launch (k_zeroshot_backward): k in 1 .. 32
@@ -1172,7 +1172,7 @@ extern "C" int vlsa_zeroshot_backward_batch(const void* bag_desc, int B, int x_d
     else
         hipLaunchKernelGGL(k_zeroshot_backward<float>, dim3(C), dim3(512), 0, s, bd, B, C, kk, idx, u, G, logits, That, tnorm, logit_scale,
                            dT, dls);
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_normalize_many(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, float* out, void* stream) {
@@ -1195,7 +1195,7 @@ extern "C" int vlsa_normalize_many(const void* X, int x_dtype, int64_t N, int64_
         return VLSA_EINVAL;
     }
 #undef VLSA_NM
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_adapter_head(const float* f, int D, const float* W1, int R, const float* W2, float keep_ratio, float* hidden,
@@ -1204,14 +1204,14 @@ extern "C" int vlsa_adapter_head(const float* f, int D, const float* W1, int R, 
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_rows_dot_relu, dim3((R + 3) / 4), dim3(256), 0, s, W1, R, D, f, (const float*)nullptr, 0.f, hidden);
     hipLaunchKernelGGL(k_rows_dot_relu, dim3((D + 3) / 4), dim3(256), 0, s, W2, D, R, hidden, f, keep_ratio, out);
-    return st();
+    return launch_status();
 }
 
 extern "C" int vlsa_topk_mean(const float* S, int C, int64_t N, int k, float out_scale, float* out, void* stream) {
     if (!S || !out || C < 1 || N < 1 || k < 1) return VLSA_EINVAL;
     if (k > kTopKMax && (int64_t)k < N) return VLSA_EUNSUPPORTED;
     hipLaunchKernelGGL(k_topk_mean, dim3(C), dim3(256), 0, (hipStream_t)stream, S, N, k, out_scale, out);
-    return st();
+    return launch_status();
 }
 
 // ---- exact Shapley values of the P text prototypes for the survival risk  v(S) = sum_k (K - k) softmax_k(ls * mean_{p in S} sim[p, k]),
@@ -1273,5 +1273,5 @@ extern "C" int vlsa_prototype_shapley(const float* sim, int P, int K, float logi
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vlsa::k_shap_values, dim3(((1u << P) + 255u) / 256u), dim3(256), 0, s, sim, P, K, logit_scale, values);
     hipLaunchKernelGGL(vlsa::k_shap_reduce, dim3(P), dim3(256), 0, s, values, P, wt, shap);
-    return st();
+    return launch_status();
 }

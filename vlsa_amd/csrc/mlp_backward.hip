@@ -29,6 +29,7 @@
 // projecter): 2.1 MFLOP per row for the gated scores = 4 x the algorithmic forward.
 #include "feat_proj.h"
 #include "gated_scores.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -500,11 +501,57 @@ int chunks_for(int n_tiles, int nsl) {
 }
 template <int MODE, bool XF32, bool POOL = false>
 int launch(const MbArgs& a, int nsl, hipStream_t st) {
-    static DeviceOnce once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)k_mlp_backward<MODE, XF32, POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, mb::kLds);
     const unsigned int grid = 8u * nsl * ((a.C + 7) / 8);
-    hipLaunchKernelGGL((k_mlp_backward<MODE, XF32, POOL>), dim3(grid), dim3(512), mb::kLds, st, a);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_mlp_backward<MODE, XF32, POOL>>(dim3(grid), dim3(512), mb::kLds, st, a);
+    return launch_status();
+}
+// What the argument blocks of the table-driven launches of this file share (MbArgs and AdxArgs name these fields alike): the bag
+// tables with dropout off ...
+template <typename Args>
+void set_tables(Args& a, const void* bag_desc, const int* tile_start, const int64_t* row_off, int B, int n_tiles) {
+    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    a.tile_start = tile_start;
+    a.row_off = reinterpret_cast<const long long*>(row_off);
+    a.B = B;
+    a.n_tiles = n_tiles;
+    a.drop_thr = 0u;
+    a.drop_scale = 1.f;
+}
+// ... the weights of the attention module as the forward packed them (vlsa_prepare_gated_weights); returns w2 ...
+template <typename Args>
+const float* set_gated_weights(Args& a, const void* prep, int gated) {
+    const GatedPrepLayout L(gated ? 1 : 0);
+    const unsigned char* pp = static_cast<const unsigned char*>(prep);
+    a.wpack = pp + L.wpack;
+    a.bias_a = reinterpret_cast<const float*>(pp + L.ba);
+    a.bias_g = reinterpret_cast<const float*>(pp + L.bg);
+    return reinterpret_cast<const float*>(pp + L.w2);
+}
+// ... and the dropout the forward ran with (false: p is no probability below 1).
+template <typename Args>
+bool set_dropout(Args& a, float p) {
+    DropSpec ds;
+    if (!drop_spec(p, &ds)) return false;
+    a.drop_thr = ds.thr;
+    a.drop_scale = ds.scale;
+    return true;
+}
+// MbArgs of a launch over n_tiles row tiles: the tables, the split into C chunks for nsl hidden slices and the chunks' partial sums in
+// the workspace (dW [U][512] per chunk, then dvec [3][512] per chunk).
+MbArgs mb_args(const void* bag_desc, const int* tile_start, const int64_t* row_off, int B, int n_tiles, int nsl, int U, void* ws) {
+    MbArgs a{};
+    set_tables(a, bag_desc, tile_start, row_off, B, n_tiles);
+    a.C = chunks_for(n_tiles, nsl);
+    a.part_w = static_cast<float*>(ws);
+    a.part_v = a.part_w + (size_t)a.C * U * 512;
+    return a;
+}
+// The fixed-order sum of the C chunks' partials: dW [U][512] and dvec [3][512], one launch each.
+int mb_reduce(const MbArgs& a, int U, float* dW, float* dvec, hipStream_t st) {
+    const long long tw = (long long)U * 512, tv = 3 * 512;
+    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
+    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tv / 4 + 31) / 32)), dim3(256), 0, st, a.part_v, a.C, tv, dvec);
+    return launch_status();
 }
 }  // namespace
 
@@ -524,44 +571,23 @@ extern "C" size_t vlsa_mlp_bwd_workspace_bytes(int mode, int n_tiles) {
 extern "C" int vlsa_attn_scores_backward(const void* bag_desc, int B, int x_dtype, int D, const void* prep, int gated,
                                          const int* tile_start, int n_tiles, const float* da, const int64_t* a_off, void* ws,
                                          float* dW, float* dvec, float drop_p, unsigned int seed, void* stream) {
-    if (!bag_desc || !prep || !tile_start || !da || !a_off || !ws || !dW || !dvec || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !prep || !da || !a_off || !ws || !dW || !dvec) return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
-    const int mode = gated ? mb::kGated : mb::kTanh, nsl = gated ? 4 : 2, U = gated ? 512 : 256;
-    const GatedPrepLayout L(gated ? 1 : 0);
-    const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    MbArgs a{};
-    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
-    a.tile_start = tile_start;
-    a.row_off = reinterpret_cast<const long long*>(a_off);
+    const int nsl = gated ? 4 : 2, U = gated ? 512 : 256;
+    MbArgs a = mb_args(bag_desc, tile_start, a_off, B, n_tiles, nsl, U, ws);
+    a.vec = set_gated_weights(a, prep, gated);
     a.rowvec = da;
-    a.wpack = pp + L.wpack;
-    a.bias_a = reinterpret_cast<const float*>(pp + L.ba);
-    a.bias_g = reinterpret_cast<const float*>(pp + L.bg);
-    a.vec = reinterpret_cast<const float*>(pp + L.w2);
-    a.B = B;
-    a.n_tiles = n_tiles;
-    a.C = chunks_for(n_tiles, nsl);
-    a.part_w = static_cast<float*>(ws);
-    a.part_v = a.part_w + (size_t)a.C * U * 512;
-    a.drop_thr = 0u;
-    a.drop_scale = 1.f;
-    if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_train
-        if (!(drop_p < 1.f)) return VLSA_EINVAL;
-        a.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
-        if (a.drop_thr == 0u) a.drop_thr = 1u;
+    if (gated && drop_p > 0.f) {
+        if (!set_dropout(a, drop_p)) return VLSA_EINVAL;
         a.drop_seed = seed;
-        a.drop_scale = 1.f / (1.f - drop_p);
     }
     hipStream_t st = (hipStream_t)stream;
     int rc;
     const bool f32 = x_dtype == VLSA_DT_F32;
-    if (mode == mb::kGated) rc = f32 ? launch<mb::kGated, true>(a, nsl, st) : launch<mb::kGated, false>(a, nsl, st);
+    if (gated) rc = f32 ? launch<mb::kGated, true>(a, nsl, st) : launch<mb::kGated, false>(a, nsl, st);
     else rc = f32 ? launch<mb::kTanh, true>(a, nsl, st) : launch<mb::kTanh, false>(a, nsl, st);
     if (rc != VLSA_OK) return rc;
-    const long long tw = (long long)U * 512, tv = 3 * 512;
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tv / 4 + 31) / 32)), dim3(256), 0, st, a.part_v, a.C, tv, dvec);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return mb_reduce(a, U, dW, dvec, st);
 }
 
 // Backward of the (gated) attention POOLING of B bags, pooled_b = softmax_b(a) X_b with a the scores above, in one pass over the rows:
@@ -576,34 +602,16 @@ extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_
                                              const float* m2, const float* l, int m_stride, const float* pooled, const float* dpooled,
                                              void* ws, float* dW, float* dvec, float* da_out, float* aw_out, float drop_p,
                                              const int64_t* seed_word, void* stream) {
-    if (!bag_desc || !prep || !tile_start || !a_raw || !a_off || !m2 || !l || !pooled || !dpooled || !ws || !dW || !dvec || B < 1 || B > 64
-        || n_tiles < 1 || m_stride < 1 || drop_p < 0.f)
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !prep || !a_raw || !a_off || !m2 || !l || !pooled || !dpooled || !ws || !dW || !dvec
+        || m_stride < 1 || drop_p < 0.f)
         return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
     const int nsl = gated ? 4 : 2, U = gated ? 512 : 256;
-    const GatedPrepLayout L(gated ? 1 : 0);
-    const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    MbArgs a{};
-    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
-    a.tile_start = tile_start;
-    a.row_off = reinterpret_cast<const long long*>(a_off);
+    MbArgs a = mb_args(bag_desc, tile_start, a_off, B, n_tiles, nsl, U, ws);
+    a.vec = set_gated_weights(a, prep, gated);
     a.rowvec = a_raw;
-    a.wpack = pp + L.wpack;
-    a.bias_a = reinterpret_cast<const float*>(pp + L.ba);
-    a.bias_g = reinterpret_cast<const float*>(pp + L.bg);
-    a.vec = reinterpret_cast<const float*>(pp + L.w2);
-    a.B = B;
-    a.n_tiles = n_tiles;
-    a.C = chunks_for(n_tiles, nsl);
-    a.part_w = static_cast<float*>(ws);
-    a.part_v = a.part_w + (size_t)a.C * U * 512;
-    a.drop_thr = 0u;
-    a.drop_scale = 1.f;
-    if (gated && drop_p > 0.f) {     // same conversion as vlsa_gated_scores_batch_train
-        if (!(drop_p < 1.f) || !seed_word) return VLSA_EINVAL;
-        a.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
-        if (a.drop_thr == 0u) a.drop_thr = 1u;
-        a.drop_scale = 1.f / (1.f - drop_p);
+    if (gated && drop_p > 0.f) {
+        if (!set_dropout(a, drop_p) || !seed_word) return VLSA_EINVAL;
         a.seed_word = reinterpret_cast<const long long*>(seed_word);
     }
     a.m2 = m2;
@@ -619,10 +627,7 @@ extern "C" int vlsa_attn_pool_backward_batch(const void* bag_desc, int B, int x_
     if (gated) rc = f32 ? launch<mb::kGated, true, true>(a, nsl, st) : launch<mb::kGated, false, true>(a, nsl, st);
     else rc = f32 ? launch<mb::kTanh, true, true>(a, nsl, st) : launch<mb::kTanh, false, true>(a, nsl, st);
     if (rc != VLSA_OK) return rc;
-    const long long tw = (long long)U * 512, tv = 3 * 512;
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tv / 4 + 31) / 32)), dim3(256), 0, st, a.part_v, a.C, tv, dvec);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return mb_reduce(a, U, dW, dvec, st);
 }
 
 // c1, c2 of the projecter's LayerNorm backward for one bag: stats [N][4] holds (mean, rstd) from the training forward
@@ -635,7 +640,7 @@ extern "C" int vlsa_feat_project_rowstats(const float* dy, int64_t lddy, const f
     hipLaunchKernelGGL(k_ln_bwd_rowstats, dim3((unsigned int)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, (long long)lddy, y,
                        (long long)ldy, (long long)N, reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta),
                        stats);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // The same for the packed rows of B <= 64 bags in one launch: y [total_rows][512] and stats [total_rows][4] hold bag b at row
@@ -649,7 +654,7 @@ extern "C" int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, cons
     hipLaunchKernelGGL(k_ln_bwd_rowstats_bags, dim3((unsigned int)((total_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const vlsa_bag_desc*>(dy_desc), B, reinterpret_cast<const long long*>(row_off), y, (long long)total_rows,
                        reinterpret_cast<const float*>(pp + L.gamma), reinterpret_cast<const float*>(pp + L.beta), stats);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // Backward of Feat_Projecter over B bags.  bag_desc / dy_desc: device tables {ptr, N, ld} of the input rows (bf16 or fp32) and of
@@ -658,33 +663,21 @@ extern "C" int vlsa_feat_project_rowstats_batch(const void* dy_desc, int B, cons
 extern "C" int vlsa_feat_project_backward(const void* bag_desc, const void* dy_desc, int B, int x_dtype, const void* prep,
                                           const int* tile_start, int n_tiles, const float* stats, const int64_t* row_off, void* ws,
                                           float* dW, float* dvec, void* stream) {
-    if (!bag_desc || !dy_desc || !prep || !tile_start || !stats || !row_off || !ws || !dW || !dvec || B < 1 || B > 64 || n_tiles < 1)
-        return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !dy_desc || !prep || !stats || !row_off || !ws || !dW || !dvec) return VLSA_EINVAL;
     if (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32) return VLSA_EUNSUPPORTED;
     const FeatProjLayout L;
     const unsigned char* pp = static_cast<const unsigned char*>(prep);
-    MbArgs a{};
-    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    MbArgs a = mb_args(bag_desc, tile_start, row_off, B, n_tiles, 4, 512, ws);
     a.dy = static_cast<const vlsa_bag_desc*>(dy_desc);
-    a.tile_start = tile_start;
-    a.row_off = reinterpret_cast<const long long*>(row_off);
     a.rowvec = stats;
     a.wpack = pp + L.wpack;
     a.bias_a = reinterpret_cast<const float*>(pp + L.bias);
     a.bias_g = nullptr;
     a.vec = reinterpret_cast<const float*>(pp + L.gamma);
-    a.B = B;
-    a.n_tiles = n_tiles;
-    a.C = chunks_for(n_tiles, 4);
-    a.part_w = static_cast<float*>(ws);
-    a.part_v = a.part_w + (size_t)a.C * 512 * 512;
     hipStream_t st = (hipStream_t)stream;
     const int rc = x_dtype == VLSA_DT_F32 ? launch<mb::kLN, true>(a, 4, st) : launch<mb::kLN, false>(a, 4, st);
     if (rc != VLSA_OK) return rc;
-    const long long tw = 512ll * 512, tv = 3 * 512;
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tw / 4 + 31) / 32)), dim3(256), 0, st, a.part_w, a.C, tw, dW);
-    hipLaunchKernelGGL(k_mb_reduce, dim3((unsigned int)((tv / 4 + 31) / 32)), dim3(256), 0, st, a.part_v, a.C, tv, dvec);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return mb_reduce(a, 512, dW, dvec, st);
 }
 
 // =================================================================================================================================
@@ -942,7 +935,7 @@ extern "C" int vlsa_prepare_attn_dx_weights(const float* Wa, const float* Wg, in
     if (!Wa || !prep_t || (gated && !Wg)) return VLSA_EINVAL;
     hipLaunchKernelGGL(k_prepare_attn_dx_weights, dim3(8 * (gated ? 16 : 8) * 8), dim3(64), 0, (hipStream_t)stream, Wa, Wg, gated ? 1 : 0,
                        static_cast<unsigned char*>(prep_t));
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // dL/dX of the (gated) attention pooling for B bags whose rows carry a gradient (see k_attn_scores_dx).  dx_desc: table of the fp32
@@ -952,50 +945,29 @@ static int attn_scores_backward_dx_impl(const void* bag_desc, const void* dx_des
                                         const void* prep_t, int gated, const int* tile_start, int n_tiles, const float* da,
                                         const float* aw, const float* dpooled, const int64_t* a_off, float drop_p, unsigned int seed,
                                         const int64_t* seed_word, void* stream) {
-    if (!bag_desc || !dx_desc || !prep || !prep_t || !tile_start || !da || !a_off || B < 1 || B > 64 || n_tiles < 1) return VLSA_EINVAL;
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !dx_desc || !prep || !prep_t || !da || !a_off) return VLSA_EINVAL;
     if ((aw == nullptr) != (dpooled == nullptr)) return VLSA_EINVAL;
     if (D != mb::kD || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) return VLSA_EUNSUPPORTED;
-    const GatedPrepLayout L(gated ? 1 : 0);
-    const unsigned char* pp = static_cast<const unsigned char*>(prep);
     AdxArgs a{};
-    a.bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    set_tables(a, bag_desc, tile_start, a_off, B, n_tiles);
+    a.w2 = set_gated_weights(a, prep, gated);
     a.dxs = static_cast<const vlsa_bag_desc*>(dx_desc);
-    a.tile_start = tile_start;
-    a.row_off = reinterpret_cast<const long long*>(a_off);
     a.da = da;
     a.aw = aw;
     a.dpooled = dpooled;
-    a.wpack = pp + L.wpack;
     a.wT = static_cast<const unsigned char*>(prep_t);
-    a.bias_a = reinterpret_cast<const float*>(pp + L.ba);
-    a.bias_g = reinterpret_cast<const float*>(pp + L.bg);
-    a.w2 = reinterpret_cast<const float*>(pp + L.w2);
-    a.B = B;
-    a.n_tiles = n_tiles;
-    a.drop_thr = 0u;
-    a.drop_scale = 1.f;
     if (gated && drop_p > 0.f) {
-        if (!(drop_p < 1.f)) return VLSA_EINVAL;
-        a.drop_thr = (unsigned int)((double)drop_p * 4294967296.0);
-        if (a.drop_thr == 0u) a.drop_thr = 1u;
+        if (!set_dropout(a, drop_p)) return VLSA_EINVAL;
         a.drop_seed = seed;
-        a.drop_scale = 1.f / (1.f - drop_p);
         a.seed_word = reinterpret_cast<const long long*>(seed_word);
     }
     hipStream_t st = (hipStream_t)stream;
-    static DeviceOnce once;
-    if (once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_attn_scores_dx<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, adx::kLds);
-        (void)hipFuncSetAttribute((const void*)k_attn_scores_dx<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, adx::kLds);
-        (void)hipFuncSetAttribute((const void*)k_attn_scores_dx<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, adx::kLds);
-        (void)hipFuncSetAttribute((const void*)k_attn_scores_dx<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, adx::kLds);
-    }
     const bool f32 = x_dtype == VLSA_DT_F32;
-#define VLSA_ADX(G, F) hipLaunchKernelGGL((k_attn_scores_dx<G, F>), dim3(n_tiles), dim3(512), adx::kLds, st, a)
-    if (gated) { if (f32) VLSA_ADX(true, true); else VLSA_ADX(true, false); }
-    else       { if (f32) VLSA_ADX(false, true); else VLSA_ADX(false, false); }
+#define VLSA_ADX(G, F) launch_lds<k_attn_scores_dx<G, F>>(dim3(n_tiles), dim3(512), adx::kLds, st, a)
+    if (gated) { if (!f32) VLSA_ADX(true, false); else VLSA_ADX(true, true); }
+    else       { if (!f32) VLSA_ADX(false, false); else VLSA_ADX(false, true); }
 #undef VLSA_ADX
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_attn_scores_backward_dx(const void* bag_desc, const void* dx_desc, int B, int x_dtype, int D, const void* prep,
@@ -1040,5 +1012,5 @@ extern "C" int vlsa_fill_one_bag_tables(void* dst, const void* X, int64_t N, int
     const int n_tiles = (int)((N + tile_rows - 1) / tile_rows);
     hipLaunchKernelGGL(vlsa::k_fill_one_bag_tables, dim3(1), dim3(64), 0, (hipStream_t)stream, static_cast<long long*>(dst), X, (long long)N,
                        (long long)ld, extra, (long long)extra_ld, n_tiles);
-    return hipGetLastError() == hipSuccess ? n_tiles : VLSA_ELAUNCH;
+    return launch_status() == VLSA_OK ? n_tiles : VLSA_ELAUNCH;
 }

@@ -8,6 +8,7 @@
 // backward: d context[(i,) o] = sum_i d out[i, pos_i(o)],  d rank[b, t] = sum_i interp[i, b] d out[i, pos_i(C + t)] with the
 // inverse map pos (deterministic: one workgroup per gradient row, ranks summed in order).
 #include "vlsa_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -106,7 +107,7 @@ extern "C" int vlsa_prompt_sentences(const float* templ, const float* context, i
     if (interp && n_base < 1) return VLSA_EINVAL;
     hipLaunchKernelGGL(k_prompt_sentences, dim3(L, R), dim3(256), 0, (hipStream_t)stream, templ, context, ctx_per_rank, rank, interp, n_base,
                        order, R, L, S, C, T, dim, out);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_prompt_sentences_backward(const float* dout, const int* pos, int ctx_per_rank, const float* interp, int n_base,
@@ -116,5 +117,5 @@ extern "C" int vlsa_prompt_sentences_backward(const float* dout, const int* pos,
     const int blocks = (ctx_per_rank ? R : 1) * C + n_rank_rows * T;
     hipLaunchKernelGGL(k_prompt_sentences_bwd, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, pos, ctx_per_rank, interp, n_base,
                        n_rank_rows, R, L, S, C, T, dim, dcontext, drank);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

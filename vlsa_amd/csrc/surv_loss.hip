@@ -4,6 +4,7 @@
 // The reference spends ~40 elementwise launches and a Python loop over the batch (convert_survival_label) on this.
 // One thread per sample; K <= 64 values live in registers / scratch -- the work is a few hundred flops per sample.
 #include "vlsa_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -276,7 +277,7 @@ extern "C" int vlsa_surv_loss(const float* x, const int64_t* t, const float* e, 
     else
         hipLaunchKernelGGL(k_surv_loss, dim3((B + kLossThreads - 1) / kLossThreads), dim3(kLossThreads), 0, (hipStream_t)stream, x, t, e, B, K, from_logits, logit_scale_exp,
                            alpha, eps, p, raw_distance, w_ifmle, w_emd, out_ifmle, out_emd, grad, (float*)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // The handler's whole objective (runner/vlsa_handler.py:241-258 with 'mean'-reduced SurvIFMLE + SurvEMD) from the raw logits in ONE
@@ -294,5 +295,5 @@ extern "C" int vlsa_surv_objective(const float* x, const int64_t* t, const float
     else
         hipLaunchKernelGGL(k_surv_loss, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, x, t, e, B, K, from_logits, logit_scale, alpha, eps, p,
                            raw_distance, w_ifmle, w_emd, (float*)nullptr, (float*)nullptr, grad, objective, ls_is_log);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

@@ -38,6 +38,7 @@
 // Backward is w.r.t. the prompt embeddings only: the tower is frozen in every shipped configuration
 // (vlsa_txt_encoder_frozen: True, cfg_vlsa_conch.yaml:69; runner/vlsa_handler.py:131).
 #include "vlsa_common.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -1897,12 +1898,8 @@ int launch_gemm_g(GemmArgs a, int M_pad, hipStream_t st) {
     a.xcd_map = NT >= 8 ? 1 : 0;      // XCD-aware block -> tile map (whole rounds of 8 tiles; the rest linear)
     size_t lds = (size_t)NW * MT * NTW * 4 * 64 * sizeof(float);
     if (PRO != PRO_NONE && lds < (size_t)(1024 + 2 * a.K) * sizeof(float)) lds = (size_t)(1024 + 2 * a.K) * sizeof(float);
-    if (lds > 64 * 1024) {
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)k_tt_gemm<MT, NW, PRO, GT, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    hipLaunchKernelGGL((k_tt_gemm<MT, NW, PRO, GT, NTW>), dim3(NT * a.MG), dim3(NW * 64), lds, st, a);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_tt_gemm<MT, NW, PRO, GT, NTW>>(dim3(NT * a.MG), dim3(NW * 64), lds, st, a);
+    return launch_status();
 }
 // G1, G2: the group counts of the CONCH-size tower for this product (compile-time specialisations); anything else: runtime G
 // wide products (N a multiple of 48): 48-column workgroup tiles, see k_tt_gemm
@@ -2033,7 +2030,7 @@ bool persist_supported(const Shape& s, const vlsa_tt_rows* r, int flags) {
 int pack_one(const float* W, int rows, int cols, int transpose, float* out, hipStream_t st) {
     const size_t n = (size_t)rows * cols;
     hipLaunchKernelGGL(k_tt_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, rows, cols, transpose, out);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 }  // namespace
@@ -2162,9 +2159,7 @@ extern "C" int vlsa_tt_forward(const vlsa_tt_model* m, const vlsa_tt_rows* r, co
         // every polled word back to zero before the launch (a memset node: replayed first under graph capture too)
         if (hipMemsetAsync(c.pctr, 0, (kPCtrWords + 8) * sizeof(unsigned), st) != hipSuccess) return VLSA_ELAUNCH;
         constexpr size_t lds = 12544 * sizeof(float);      // max(reduction 8 x 24 x 64, attention 3 x 64 x 65, LayerNorm scratch)
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)k_tt_forward_persistent, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_tt_forward_persistent, dim3(grid), dim3(512), lds, st, a);
+        launch_lds<k_tt_forward_persistent>(dim3(grid), dim3(512), lds, st, a);
         TT_LAUNCHED();
         if (save_for_backward) {            // the backward pass reads tiled copies of every block's x_in / x_mid: made here from the rows the
             for (int L = 0; L < s.layers; ++L) {            // persistent launch kept (an opt-in, slower path anyway: 24 small launches)
@@ -2272,7 +2267,7 @@ int launch_dw(int bsrc, const float* dY_t, const float* act, int ldb, float* dW,
     const dim3 grid(K / 64, N / 128);
     if (bsrc == DW_TILED) hipLaunchKernelGGL(k_tt_dw<DW_TILED>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_tt_dw<DW_ROWS>, grid, dim3(256), 0, st, a);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // gr != null: ALSO the gradients of the tower's own parameters, written (not accumulated) into the buffers gr points at -- a
@@ -2318,7 +2313,6 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
                            (float*)gr->lnf_w, (float*)gr->lnf_b);
         TT_LAUNCHED();
     }
-    static DeviceOnce once;
     bool scattered = false;
     // Round 6: shared prefix, <= 128 compact rows (M; M_pad may be larger), and the extra L x heads workgroups still fit one round of the CUs: the prefix keys'
     // dK / dV come from a workgroup per (key, head) over all query rows (the forward's attention statistics + output) instead of the
@@ -2342,7 +2336,6 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
     if (const char* e = VLSA_ENV("VLSA_TT_ATTN_GRID")) attn_grid_x = atoi(e);
 #endif
     const int attn_grid = attn_grid_x;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)k_tt_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_stats > lds_ticket ? lds_stats : lds_ticket));
     // Round 6: with frozen weights and the CONCH shapes (d = 768: a wave's 192-column slab = 12 groups; few rows: the 16 x 96 / 16 x 32
     // products) both LayerNorm backward passes of a block run as PROLOGUES of the products that consume their result (PRO_LNBWD):
     //   ln_2 backward  -> in front of  d attn = dx_mid W_out          (this block)
@@ -2389,7 +2382,7 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
             prefetch_for(a, true, pw.in_w, d, 3 * d, 2);
             TT_TRY((launch_gemm_g<1, 4, PRO_LNBWD, 12, 2>(a, Mp, st)));
         }
-        hipLaunchKernelGGL(k_tt_attn_bwd, dim3(attn_grid), dim3(attn_threads(r->max_len)), attn_lds_x, st, qkv, 3 * d, c.dattn, attn_bwd_ldo(d),
+        launch_lds<k_tt_attn_bwd>(dim3(attn_grid), dim3(attn_threads(r->max_len)), attn_lds_x, st, qkv, 3 * d, c.dattn, attn_bwd_ldo(d),
                            c.dqkv_t, r->seq_row0, r->cls_keep, s.heads, d, s.n_seq, s.L, c.pfx, c.cnt, layer_attn_t(x_in, s), layer_astats(x_in, s),
                            r->row_seq, s.M, use_stats);
         TT_LAUNCHED();
@@ -2466,7 +2459,7 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
             a.Y = c.dattn; a.ldy = d;
             TT_TRY((launch_gemm_rows16<4, 12>(a, s.M, Mp, st)));
         }
-        hipLaunchKernelGGL(k_tt_attn_bwd, dim3(attn_grid), dim3(attn_threads(r->max_len)), attn_lds, st, qkv, 3 * d, c.dattn, d,
+        launch_lds<k_tt_attn_bwd>(dim3(attn_grid), dim3(attn_threads(r->max_len)), attn_lds, st, qkv, 3 * d, c.dattn, d,
                            c.dqkv_t, r->seq_row0, r->cls_keep, s.heads, d, s.n_seq, s.L, c.pfx, c.cnt, layer_attn_t(x_in, s), layer_astats(x_in, s),
                            r->row_seq, s.M, use_stats);
         TT_LAUNCHED();
@@ -2491,10 +2484,10 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
                            (float*)gr->pos_emb, (float*)gr->cls_emb);
         TT_LAUNCHED();
     }
-    if (scattered) return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    if (scattered) return launch_status();
     if (hipMemsetAsync(demb, 0, (size_t)demb_floats * sizeof(float), st) != hipSuccess) return VLSA_ELAUNCH;
     hipLaunchKernelGGL(k_tt_scatter, dim3(s.M), dim3(256), 0, st, c.dxa, d, demb, emb_seq_stride, emb_tok_stride, r->row_seq, r->row_src, s.M);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 }  // namespace
 

@@ -11,6 +11,7 @@
 // raw queries is P x D work and stays on the host side (vlsa_amd/functional.py).  Partials are plain sums; they
 // are reduced with vlsa_vlfan_merge (pm = 0, pl = 1, normalise = 0).
 #include "vlfan_mfma_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -261,21 +262,13 @@ extern "C" int vlsa_vlfan_backward(const void* X, int x_dtype, int64_t N, int64_
     const QPrepLayout L(D);
     const __bf16* qsplit = reinterpret_cast<const __bf16*>(static_cast<const unsigned char*>(qprep) + L.qsplit);
     if (x_dtype == VLSA_DT_F32) {
-        auto kern = k_vlfan_backward_mfma<float>;
-        constexpr int lds = bwd_lds_bytes<true>();
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, s, (const float*)X, N, ldx, qsplit, dsplit, P, m2, l, delta,
+        launch_lds<k_vlfan_backward_mfma<float>>(dim3(G), dim3(256), bwd_lds_bytes<true>(), s, (const float*)X, N, ldx, qsplit, dsplit, P, m2, l, delta,
                            coattn_scale, pm, pl, pacc, G, static_cast<const vlsa_bag_desc*>(nullptr));
     } else {
-        auto kern = k_vlfan_backward_mfma<__bf16>;
-        constexpr int lds = bwd_lds_bytes<false>();
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, s, (const __bf16*)X, N, ldx, qsplit, dsplit, P, m2, l, delta,
+        launch_lds<k_vlfan_backward_mfma<__bf16>>(dim3(G), dim3(256), bwd_lds_bytes<false>(), s, (const __bf16*)X, N, ldx, qsplit, dsplit, P, m2, l, delta,
                            coattn_scale, pm, pl, pacc, G, static_cast<const vlsa_bag_desc*>(nullptr));
     }
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 // The per-bag kernel over a table of bags in ONE launch (see vlsa_bag_desc): dsplit [B][3][16][D] and delta [B][16] as produced by
@@ -285,19 +278,11 @@ int vlsa_launch_backward_mfma_bags(const void* bag_desc, int B, int x_dtype, con
                                    float* pacc, int G, hipStream_t s) {
     const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
     if (x_dtype == VLSA_DT_F32) {
-        auto kern = k_vlfan_backward_mfma<float>;
-        constexpr int lds = bwd_lds_bytes<true>();
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(kern, dim3(G, B), dim3(256), lds, s, static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0, qsplit, dsplit, P,
+        launch_lds<k_vlfan_backward_mfma<float>>(dim3(G, B), dim3(256), bwd_lds_bytes<true>(), s, static_cast<const float*>(nullptr), (int64_t)0, (int64_t)0, qsplit, dsplit, P,
                            m2, l, delta, scale, pm, pl, pacc, G, bags);
     } else {
-        auto kern = k_vlfan_backward_mfma<__bf16>;
-        constexpr int lds = bwd_lds_bytes<false>();
-        static DeviceOnce once;
-        if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipLaunchKernelGGL(kern, dim3(G, B), dim3(256), lds, s, static_cast<const __bf16*>(nullptr), (int64_t)0, (int64_t)0, qsplit, dsplit, P,
+        launch_lds<k_vlfan_backward_mfma<__bf16>>(dim3(G, B), dim3(256), bwd_lds_bytes<false>(), s, static_cast<const __bf16*>(nullptr), (int64_t)0, (int64_t)0, qsplit, dsplit, P,
                            m2, l, delta, scale, pm, pl, pacc, G, bags);
     }
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }

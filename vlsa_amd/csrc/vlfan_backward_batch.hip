@@ -17,6 +17,7 @@
 #endif
 #define VLSA_STREAM_NT VLSA_DMA_NT
 #include "vlfan_stream.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -336,12 +337,9 @@ extern "C" int vlsa_vlfan_backward_batch(const void* bag_desc, int B, int x_dtyp
     }
     if (x_dtype == VLSA_DT_F32)
         return vlsa_launch_backward_f32_batch(bag_desc, B, qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, S, s);
-    static DeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)k_vlfan_backward_dma_batch, hipFuncAttributeMaxDynamicSharedMemorySize, bb::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_backward_dma_batch, dim3(512), dim3(256), bb::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
-                       qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, S);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_vlfan_backward_dma_batch>(dim3(512), dim3(256), bb::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
+                                           qsplit, dsplit, P, m2, l, delta, coattn_scale, pm, pl, pacc, S);
+    return launch_status();
 }
 
 int vlsa_launch_backward_mfma_bags(const void* bag_desc, int B, int x_dtype, const __bf16* qsplit, const __bf16* dsplit, int P,

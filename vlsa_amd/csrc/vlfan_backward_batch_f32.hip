@@ -17,6 +17,7 @@
 // No P <= 12 restriction here (the exchange tiles are the full 16 x 16).
 #define VLSA_STREAM_NT "nt"
 #include "vlfan_stream.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -260,10 +261,7 @@ using namespace vlsa;
 int vlsa_launch_backward_f32_batch(const void* bag_desc, int B, const __bf16* qsplit, const __bf16* dsplit, int P,
                                    const float* m2, const float* l, const float* delta, float scale, float* pm, float* pl,
                                    float* pacc, int S, hipStream_t s) {
-    static DeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)k_vlfan_backward_f32_batch, hipFuncAttributeMaxDynamicSharedMemorySize, bbf::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_backward_f32_batch, dim3(512), dim3(256), bbf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
-                       qsplit, dsplit, P, m2, l, delta, scale, pm, pl, pacc, S);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_vlfan_backward_f32_batch>(dim3(512), dim3(256), bbf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(bag_desc), B,
+                                           qsplit, dsplit, P, m2, l, delta, scale, pm, pl, pacc, S);
+    return launch_status();
 }

@@ -17,6 +17,7 @@
 #endif
 #define VLSA_STREAM_NT VLSA_DMA_NT
 #include "vlfan_stream.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -690,7 +691,7 @@ static int launch_merge_pool(const float* pm, const float* pl, const float* pacc
     else
         hipLaunchKernelGGL(k_vlfan_merge_pool_batch, dim3((D + 63) / 64, B), dim3(512), 0, s, pm, pl, pacc, G, P, D, m2, l, out, st,
                            pool_mode, pool_w, pooled);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 #ifdef VLSA_TIMING
@@ -780,11 +781,6 @@ extern "C" int vlsa_vlfan_partial_batch_scores(const void* bag_desc, int B, int 
     float* pm = static_cast<float*>(workspace);
     float* pl = pm + (size_t)B * G * kPStride;
     float* pacc = pl + (size_t)B * G * kPStride;
-    static DeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_dma_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bt::kLdsBytes);
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_dma_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bt::kLdsBytes);
-    }
     const QPrepLayout L(D);
     if (x_dtype == VLSA_DT_F32) {
         const unsigned char* qp = static_cast<const unsigned char*>(qprep);
@@ -798,15 +794,15 @@ extern "C" int vlsa_vlfan_partial_batch_scores(const void* bag_desc, int B, int 
 #else
     constexpr int xm = 0;
 #endif
-    if (scores_desc)
-        hipLaunchKernelGGL(k_vlfan_partial_dma_batch<true>, dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
-                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S,
-                           static_cast<const vlsa_rows_desc*>(scores_desc));
+    if (!scores_desc)
+        launch_lds<k_vlfan_partial_dma_batch<false>>(dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
+                                                     static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S | (xm << 8),
+                                                     static_cast<const vlsa_rows_desc*>(nullptr));
     else
-        hipLaunchKernelGGL(k_vlfan_partial_dma_batch<false>, dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
-                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S | (xm << 8),
-                           static_cast<const vlsa_rows_desc*>(nullptr));
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+        launch_lds<k_vlfan_partial_dma_batch<true>>(dim3(WG), dim3(512), bt::kLdsBytes, (hipStream_t)stream,
+                                                    static_cast<const vlsa_bag_desc*>(bag_desc), B, qsplit, P, pm, pl, pacc, S,
+                                                    static_cast<const vlsa_rows_desc*>(scores_desc));
+    return launch_status();
 }
 
 extern "C" int vlsa_vlfan_partial_batch_ex(const void* bag_desc, int B, int x_dtype, int D, const void* qprep, int P,
@@ -823,7 +819,7 @@ extern "C" int vlsa_attn_normalise_batch(const void* bag_desc, int B, int P, int
     hipLaunchKernelGGL(k_attn_normalise_batch, dim3(chunks, P, B), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const vlsa_bag_desc*>(bag_desc), static_cast<const vlsa_rows_desc*>(scores_desc),
                        static_cast<const vlsa_rows_desc*>(attn_desc), m2, l, (int)kPStride);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_vlfan_partial_batch(const void* bag_desc, int B, int x_dtype, int D, const void* qprep, int P,
@@ -882,7 +878,7 @@ extern "C" int vlsa_vlfan_merge_batch_strided(const float* pm, const float* pl, 
         return VLSA_EINVAL;
     hipLaunchKernelGGL(k_vlfan_merge_batch, dim3((D + 511) / 512, P, B), dim3(256), 0, (hipStream_t)stream, pm, pl, pacc, G, P, D,
                        normalise, m2, l, out, st);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_vlfan_merge_head_batch_strided(const float* pm, const float* pl, const float* pacc, int B, int G, int P, int D,

@@ -14,6 +14,7 @@
 // cycles; with the sum in f32 as well (round 1) it was 2048 = ~95 % of the pipe at HBM rate, and the kernel sat at 62-64 %.
 #define VLSA_STREAM_NT "nt"
 #include "vlfan_stream.h"
+#include "launch.h"
 #ifndef VLSA_F32_ABL
 #define VLSA_F32_ABL 0     // timing-only ablations / schedule variants (tools/f32_ablate.py); 0 = the product
 #endif
@@ -358,20 +359,15 @@ using namespace vlsa;
 
 int vlsa_launch_partial_f32_batch(const void* bag_desc, int B, const float* qeff, const float* qmeta, int P, float* pm,
                                   float* pl, float* pacc, int S, int workgroups, const void* scores_desc, hipStream_t s) {
-    static DeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_f32_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bf::kLdsBytes);
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_f32_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bf::kLdsBytes);
-    }
-    if (scores_desc)
-        hipLaunchKernelGGL(k_vlfan_partial_f32_batch<true>, dim3(workgroups), dim3(512), bf::kLdsBytes, s,
-                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
-                           static_cast<const vlsa_rows_desc*>(scores_desc), vlsa_bag_desc{nullptr, 0, 0});
+    if (!scores_desc)
+        launch_lds<k_vlfan_partial_f32_batch<false>>(dim3(workgroups), dim3(512), bf::kLdsBytes, s,
+                                                     static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
+                                                     static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{nullptr, 0, 0});
     else
-        hipLaunchKernelGGL(k_vlfan_partial_f32_batch<false>, dim3(workgroups), dim3(512), bf::kLdsBytes, s,
-                           static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
-                           static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{nullptr, 0, 0});
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+        launch_lds<k_vlfan_partial_f32_batch<true>>(dim3(workgroups), dim3(512), bf::kLdsBytes, s,
+                                                    static_cast<const vlsa_bag_desc*>(bag_desc), B, qeff, qmeta, P, pm, pl, pacc, S,
+                                                    static_cast<const vlsa_rows_desc*>(scores_desc), vlsa_bag_desc{nullptr, 0, 0});
+    return launch_status();
 }
 
 // ONE fp32 bag through the same kernel (the drop-in's bag-by-bag calls, runner/vlsa_handler.py:322-330): G workgroups, G partials
@@ -379,10 +375,7 @@ int vlsa_launch_partial_f32_batch(const void* bag_desc, int B, const float* qeff
 // no descriptor table has to be uploaded.  No score output (its rows would need the padded pitch of vlsa_rows_desc).
 int vlsa_launch_partial_f32_one(const float* X, int64_t N, int64_t ldx, const float* qeff, const float* qmeta, int P, float* pm,
                                 float* pl, float* pacc, int G, hipStream_t s) {
-    static DeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_f32_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bf::kLdsBytes);
-    hipLaunchKernelGGL(k_vlfan_partial_f32_batch<false>, dim3(G), dim3(512), bf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(nullptr), 1,
-                       qeff, qmeta, P, pm, pl, pacc, 1, static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{X, N, ldx});
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_vlfan_partial_f32_batch<false>>(dim3(G), dim3(512), bf::kLdsBytes, s, static_cast<const vlsa_bag_desc*>(nullptr), 1,
+                                                 qeff, qmeta, P, pm, pl, pacc, 1, static_cast<const vlsa_rows_desc*>(nullptr), vlsa_bag_desc{X, N, ldx});
+    return launch_status();
 }

@@ -23,6 +23,7 @@
 // All products are exact f32 (v_mfma_f32_16x16x4_f32): 512 steps x 32 cycles per 16-row tile = 6.8 us per wave-tile, i.e.
 // ~21 us per 50k-patch bag on 1024 waves -- about the HBM time of the 205 MB it moves (26 us at 8 TB/s).
 #include "bag_table.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -233,8 +234,6 @@ extern "C" int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc,
         return VLSA_EINVAL;
     if (D != dx::kD) return VLSA_EUNSUPPORTED;
     if (P < 1 || P > VLSA_MAX_P) return VLSA_EINVAL;
-    static DeviceOnce once;
-    if (once.first()) (void)hipFuncSetAttribute((const void*)k_vlfan_dx, hipFuncAttributeMaxDynamicSharedMemorySize, dx::kLds);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_dx_delta, dim3(B), dim3(1024), 0, st, dout, out, P, delta_ws);
     DxArgs a{};
@@ -252,6 +251,6 @@ extern "C" int vlsa_vlfan_backward_dx(const void* bag_desc, const void* dx_desc,
     a.P = P;
     a.n_tiles = n_tiles;
     const int G = n_tiles < 256 ? n_tiles : 256;
-    hipLaunchKernelGGL(k_vlfan_dx, dim3(G), dim3(256), dx::kLds, st, a);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_vlfan_dx>(dim3(G), dim3(256), dx::kLds, st, a);
+    return launch_status();
 }

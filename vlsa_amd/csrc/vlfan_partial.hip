@@ -13,6 +13,7 @@
 //                            bf16 MFMA rate; the kernel is HBM-bound (1 KB / 2 KB per patch row).
 //   k_vlfan_partial_generic  any D <= 1024 (D % 8 == 0), fp32 VALU; fallback + on-device cross-check.
 #include "vlfan_mfma_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -454,7 +455,7 @@ extern "C" int vlsa_prepare_queries(const float* Q, int nq, int D, int gated, fl
     hipLaunchKernelGGL(k_prepare_queries, dim3(17), dim3(256), 0, (hipStream_t)stream, Q, nq, D, gated,
                        coattn_scale * kLog2e, static_cast<unsigned char*>(qprep), (const float*)nullptr, (float*)nullptr,
                        (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 extern "C" int vlsa_prepare_queries_and_text(const float* Q, int nq, int D, int gated, float coattn_scale, void* qprep,
@@ -464,7 +465,7 @@ extern "C" int vlsa_prepare_queries_and_text(const float* Q, int nq, int D, int 
     if (P < 1 || P > VLSA_MAX_P || !(coattn_scale > 0.f)) return VLSA_EINVAL;
     hipLaunchKernelGGL(k_prepare_queries, dim3(17 + K), dim3(256), 0, (hipStream_t)stream, Q, nq, D, gated,
                        coattn_scale * kLog2e, static_cast<unsigned char*>(qprep), T, That, tnorm);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 template <typename XT>
@@ -474,16 +475,14 @@ static int launch_generic(const XT* X, int64_t N, int64_t ldx, int D, const floa
 #define VLSA_GEN(DPL)                                                                                              \
     {                                                                                                              \
         const size_t lds = (32 + (size_t)16 * DPL * 64) * sizeof(float);                                           \
-        auto kern = k_vlfan_partial_generic<XT, DPL>;                                                              \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, X, N, ldx, D, qeff, P, qmeta, pm, pl, pacc, scores, G);     \
+        launch_lds<k_vlfan_partial_generic<XT, DPL>>(grid, block, lds, s, X, N, ldx, D, qeff, P, qmeta, pm, pl, pacc, scores, G); \
     }
     if (D <= 256) VLSA_GEN(4)
     else if (D <= 512) VLSA_GEN(8)
     else if (D <= 768) VLSA_GEN(12)
     else VLSA_GEN(16)
 #undef VLSA_GEN
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    return launch_status();
 }
 
 template <typename XT>
@@ -491,13 +490,8 @@ static int launch_mfma(const XT* X, int64_t N, int64_t ldx, const __bf16* qsplit
                        float* pl, float* pacc, float* scores, int G, hipStream_t s) {
     constexpr bool F32 = sizeof(XT) == 4;
     constexpr int lds = mfma_lds_bytes<F32>();
-    auto kern = k_vlfan_partial_mfma<XT>;
-    static DeviceOnce attr_once;
-    if (lds > 64 * 1024 && attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-    hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, s, X, N, ldx, qsplit, P, pm, pl, pacc, scores, G);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+    launch_lds<k_vlfan_partial_mfma<XT>>(dim3(G), dim3(256), lds, s, X, N, ldx, qsplit, P, pm, pl, pacc, scores, G);
+    return launch_status();
 }
 
 int vlsa_launch_partial_dma(const __bf16* X, int64_t N, int64_t ldx, const __bf16* qsplit_scaled, int P, float* pm,

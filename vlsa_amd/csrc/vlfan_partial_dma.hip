@@ -15,6 +15,7 @@
 //   * counted s_waitcnt vmcnt(N) + raw s_barrier keep the next tile's DMA in flight across the exchange.
 #define VLSA_STREAM_NT ""      // no cache qualifier on the single-bag kernel's DMA loads
 #include "vlfan_stream.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -357,20 +358,13 @@ extern "C" int vlsa_debug_read_cycles(long long* host_out) {
 // Called from vlsa_vlfan_partial (vlfan_partial.hip).
 int vlsa_launch_partial_dma(const __bf16* X, int64_t N, int64_t ldx, const __bf16* qsplit_scaled, int P, float* pm,
                             float* pl, float* pacc, float* scores, int G, hipStream_t s) {
-    static DeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_dma<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  dma::kLdsBytes);
-        (void)hipFuncSetAttribute((const void*)k_vlfan_partial_dma<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  dma::kLdsBytes);
-    }
     const int64_t units = (N + 15) >> 4;
     const int uq = (int)(units / G), ur = (int)(units % G);
-    if (scores != nullptr)
-        hipLaunchKernelGGL(k_vlfan_partial_dma<true>, dim3(G), dim3(512), dma::kLdsBytes, s, X, N, ldx, qsplit_scaled, P, pm,
-                           pl, pacc, scores, uq, ur);
+    if (scores == nullptr)
+        launch_lds<k_vlfan_partial_dma<false>>(dim3(G), dim3(512), dma::kLdsBytes, s, X, N, ldx, qsplit_scaled, P, pm,
+                                               pl, pacc, scores, uq, ur);
     else
-        hipLaunchKernelGGL(k_vlfan_partial_dma<false>, dim3(G), dim3(512), dma::kLdsBytes, s, X, N, ldx, qsplit_scaled, P, pm,
-                           pl, pacc, scores, uq, ur);
-    return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH;
+        launch_lds<k_vlfan_partial_dma<true>>(dim3(G), dim3(512), dma::kLdsBytes, s, X, N, ldx, qsplit_scaled, P, pm,
+                                              pl, pacc, scores, uq, ur);
+    return launch_status();
 }

@@ -3,6 +3,7 @@
 // All of it is P x D / D x D sized work; the design goal is few launches and no single-workgroup serial
 // stretch longer than a few microseconds (MI355X_MICROARCH.md: kernel boundary ~1.5-1.9 us).
 #include "vlsa_common.h"
+#include "launch.h"
 
 namespace vlsa {
 
@@ -694,8 +695,6 @@ extern "C" const char* vlsa_error_string(int code) {
         default: return "unknown error";
     }
 }
-
-static inline int launch_status() { return hipGetLastError() == hipSuccess ? VLSA_OK : VLSA_ELAUNCH; }
 
 extern "C" int vlsa_vlfan_merge_strided(const float* pm, int64_t pm_stride, const float* pl, int64_t pl_stride,
                                         const float* pacc, int64_t pacc_stride, int G, int P, int D, int normalise,
