@@ -349,6 +349,36 @@ int vlsa_scored_pool_partial(const void* X, int x_dtype, int64_t N, int64_t ldx,
 int vlsa_colmax(const void* X, int x_dtype, int64_t N, int64_t ldx, int D, float* partials, float* out, void* stream);
 
 /*
+ * MaxMIL / MeanMIL over a TABLE of B <= 64 bags (model/deepmil.py:57-60,271-274 per bag): bag_desc = device table of vlsa_bag_desc
+ * (bf16 or fp32 rows, N >= 1, row stride >= 512, 16-byte aligned rows), D == 512.  VLSA_EINVAL: a NULL pointer, B outside [1, 64], a
+ * table with fewer parts / tiles than bags, another mode; VLSA_EUNSUPPORTED: D != 512, another dtype -- before anything is launched.
+ *
+ * vlsa_colmax_batch: out [B][512] fp32 = the column maxima of every bag and idx [B][512] int32 = the row WITHIN THE BAG each came
+ *   from, as torch.max(X, dim=1) names it: the FIRST maximal row (every comparison is a strict > over rows in ascending order; -0.0
+ *   against +0.0 is a tie).  A column of -inf, or of the most negative finite value, still returns a valid row.  NaN rows are out of
+ *   contract, as for vlsa_colmax.  part_start [B + 1] int32 (device): bag b owns the parts part_start[b] .. part_start[b + 1],
+ *   vlsa_colmax_parts(N_b) = clamp(ceil(N_b / vlsa_colmax_part_rows()), 1, 512) of them -- a function of N_b alone, so a bag's result
+ *   is the same alone and in any batch (its G parts are contiguous row ranges of N / G rows, the first N mod G of them one row
+ *   more); n_parts = part_start[B].  workspace: vlsa_colmax_workspace_bytes(n_parts), no initialisation.
+ *   Two launches (one workgroup per part; one merge that walks a bag's parts in part order), no atomics.
+ * vlsa_pool_dx_batch: the dense fp32 row gradient of all bags in one launch, every element written exactly once (no memset, no
+ *   atomics): dx_desc = device table {pointer, N, row stride >= 512} of the fp32 gradient rows, bag_desc = the bags' own table (its
+ *   N is read); mode 0 (mean): dpooled[b][d] / N_b in every row; mode 1 (max): dpooled[b][d] in row idx[b][d], 0 elsewhere (idx NULL
+ *   allowed for mode 0).  tile_start [B + 1] int32 in tiles of vlsa_pool_dx_tile_rows() rows, n_tiles = tile_start[B].
+ * vlsa_gather_rows_batch: out fp32 [B * 512][512], row 512 b + d = row idx[b][d] of bag b (bf16 widens exactly; an index outside
+ *   the bag gives a row of zeros).
+ */
+int vlsa_colmax_part_rows(void);
+int vlsa_colmax_parts(int64_t N);
+size_t vlsa_colmax_workspace_bytes(int n_parts);
+int vlsa_colmax_batch(const void* bag_desc, int B, int x_dtype, int D, const int* part_start, int n_parts, void* workspace, float* out,
+                      int* idx, void* stream);
+int vlsa_pool_dx_tile_rows(void);
+int vlsa_pool_dx_batch(const void* dx_desc, const void* bag_desc, int B, int mode, const int* idx, const float* dpooled,
+                       const int* tile_start, int n_tiles, void* stream);
+int vlsa_gather_rows_batch(const void* bag_desc, int B, int x_dtype, const int* idx, float* out, void* stream);
+
+/*
  * Replaces the elementwise part of Attention_Pooling / Gated_Attention_Pooling scoring (model/layers.py:110-113,
  * 144): a[n] = w2 . (tanh(H[n] + b1) [* sigmoid(Hg[n] + bg)]) + b2, H = x W1^T (and Hg = x Wg^T) being plain
  * [N,512]x[512,hid] GEMMs done by the caller (rocBLAS).  Hg/bg NULL => ungated.

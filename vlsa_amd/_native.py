@@ -138,6 +138,13 @@ _SIGNATURES = {
     "vlsa_scored_pool_partial": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
     "vlsa_colmax": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vlsa_colmax_part_rows": (c_int, []),
+    "vlsa_colmax_parts": (c_int, [c_int64]),
+    "vlsa_colmax_workspace_bytes": (c_size_t, [c_int]),
+    "vlsa_colmax_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vlsa_pool_dx_tile_rows": (c_int, []),
+    "vlsa_pool_dx_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vlsa_gather_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vlsa_attn_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
     "vlsa_query_pool_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

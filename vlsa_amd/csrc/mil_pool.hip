@@ -9,6 +9,7 @@
 // All of them are HBM-bound streaming reductions: one wave per patch row, 16-byte (bf16) / 8-byte loads per
 // lane are not needed here because a row is spread over the 64 lanes with unit stride (fully coalesced).
 #include "vlsa_common.h"
+#include "bag_table.h"
 #include "launch.h"
 
 namespace vlsa {
@@ -897,6 +898,176 @@ __global__ __launch_bounds__(512) void k_zeroshot_backward(const vlsa_bag_desc* 
         if (tid == 0) *dls = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
     }
 }
+
+// ---- MaxMIL / MeanMIL over a bag table: column max WITH the row it came from, the dense row gradient of both poolings and the gather
+// of the selected rows.  torch.max(X, dim=1) (model/deepmil.py:59-60,273-274) hands its gradient to the FIRST maximal row of a
+// column, so every comparison below is a strict > over rows (parts, waves) taken in ascending order: an equal value never replaces
+// an earlier one, and -0.0 against +0.0 is a tie.  A running (value, row) pair is seeded from a real row -- the part's first, the
+// bag's first part -- never from -inf without a row: a column of -inf still names row 0.  NaN rows are out of contract.
+constexpr int kColmaxPartRows = 64, kColmaxMaxParts = 512;     // rows per part of a bag (more once the cap is reached), parts per bag
+constexpr int kPoolDxTileRows = 64;                            // rows of dX one workgroup of k_pool_dx writes
+
+// Level one: workgroup = one part of one bag.  Wave w streams the w-th contiguous quarter of the part's rows, 4 rows (16 bytes per
+// lane and chunk) in flight, a lane keeps the pair of each of its 8 columns (unit_col<XT>); the four waves' pairs meet in LDS and
+// are folded in wave order, i.e. in row order.  Every wave starts from the part's first row, so a wave without rows of its own
+// (a part of fewer than 4 rows) hands on that pair and changes nothing.
+template <typename XT>
+__global__ __launch_bounds__(256) void k_colmax_idx_partial(const vlsa_bag_desc* __restrict__ bags, int B, const int* __restrict__ part_start,
+                                                             float* __restrict__ pval, int* __restrict__ pidx) {
+    constexpr int U = 4;
+    __shared__ float sval[4][512];
+    __shared__ int sidx[4][512];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const BagSpan part = bag_span(part_start, B, blockIdx.x);
+    if (part.idx >= part.count) return;                        // (a grid larger than the table: nothing to do, nothing read)
+    const vlsa_bag_desc d = bags[part.b];
+    const XT* X = static_cast<const XT*>(d.X);
+    int64_t pbeg, pend, q0, q1;
+    rows_of_block(d.N, part.idx, part.count, pbeg, pend);
+    rows_of_block(pend - pbeg, w, 4, q0, q1);
+    const int64_t rbeg = pbeg + q0, rend = pbeg + q1;
+    float mx[8];
+    int mi[8];
+    load_row_512<XT>(X + pbeg * d.ldx, lane, mx);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mi[j] = (int)pbeg;
+    for (int64_t r0 = rbeg; r0 < rend; r0 += U) {
+        float v[U][8];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t r = r0 + u < rend ? r0 + u : rend - 1;      // the tail re-reads the last row: an equal value changes nothing
+            load_row_512<XT>(X + r * d.ldx, lane, v[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int r = (int)(r0 + u < rend ? r0 + u : rend - 1);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (v[u][j] > mx[j]) {
+                    mx[j] = v[u][j];
+                    mi[j] = r;
+                }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = unit_col<XT>(lane, j);
+        sval[w][c] = mx[j];
+        sidx[w][c] = mi[j];
+    }
+    __syncthreads();
+    for (int c = tid; c < 512; c += 256) {
+        float bv = sval[0][c];
+        int bi = sidx[0][c];
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (sval[k][c] > bv) {
+                bv = sval[k][c];
+                bi = sidx[k][c];
+            }
+        pval[(size_t)blockIdx.x * 512 + c] = bv;
+        pidx[(size_t)blockIdx.x * 512 + c] = bi;
+    }
+}
+
+// Level two: workgroup (x, b) = 128 columns of bag b; thread (q, c) walks the q-th contiguous quarter of the bag's parts in part
+// order, seeded from the bag's first part, and the four quarters are folded in order.
+__global__ __launch_bounds__(512) void k_colmax_idx_merge(const int* __restrict__ part_start, const float* __restrict__ pval,
+                                                           const int* __restrict__ pidx, float* __restrict__ out, int* __restrict__ idx) {
+    __shared__ float sval[4][128];
+    __shared__ int sidx[4][128];
+    const int b = blockIdx.y, cl = threadIdx.x & 127, q = threadIdx.x >> 7, c = blockIdx.x * 128 + cl;
+    const int p0 = part_start[b], G = part_start[b + 1] - p0;
+    int64_t g0, g1;
+    rows_of_block(G, q, 4, g0, g1);
+    float bv = pval[(size_t)p0 * 512 + c];
+    int bi = pidx[(size_t)p0 * 512 + c];
+#pragma unroll 8
+    for (int64_t g = g0; g < g1; ++g) {
+        const float v = pval[(size_t)(p0 + g) * 512 + c];
+        const int i = pidx[(size_t)(p0 + g) * 512 + c];
+        if (v > bv) {
+            bv = v;
+            bi = i;
+        }
+    }
+    sval[q][cl] = bv;
+    sidx[q][cl] = bi;
+    __syncthreads();
+    if (q == 0) {
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            if (sval[k][cl] > bv) {
+                bv = sval[k][cl];
+                bi = sidx[k][cl];
+            }
+        out[(size_t)b * 512 + c] = bv;
+        idx[(size_t)b * 512 + c] = bi;
+    }
+}
+
+// Dense row gradient of mean (kMax false: dpooled[b] / N_b in every row) or max pooling (dpooled[b][d] in row idx[b][d] of column d,
+// 0 elsewhere) of all bags: workgroup = one tile of kPoolDxTileRows rows of one bag, a lane holds the gradient and the index of its 8
+// columns in registers and writes every element of the tile exactly once, 16 bytes per store; wave w takes rows w, w + 4, ...
+template <bool kMax>
+__global__ __launch_bounds__(256) void k_pool_dx(const vlsa_bag_desc* __restrict__ dx, const vlsa_bag_desc* __restrict__ bags, int B,
+                                                  const int* __restrict__ tile_start, const int* __restrict__ idx,
+                                                  const float* __restrict__ dpooled) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const BagSpan tile = bag_span(tile_start, B, blockIdx.x);
+    if (tile.idx >= tile.count) return;
+    const vlsa_bag_desc o = dx[tile.b];
+    const int64_t N = bags[tile.b].N;
+    float* out = static_cast<float*>(const_cast<void*>(o.X));
+    f32x4 g[2];
+    i32x4 sel[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int col = (64 * c + lane) * 4;
+        g[c] = *reinterpret_cast<const f32x4*>(dpooled + (size_t)tile.b * 512 + col);
+        if constexpr (kMax) sel[c] = *reinterpret_cast<const i32x4*>(idx + (size_t)tile.b * 512 + col);
+        else {
+            const float n = (float)N;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) g[c][e] = g[c][e] / n;
+        }
+    }
+    const int64_t r0 = (int64_t)tile.idx * kPoolDxTileRows;
+    const int64_t r1 = r0 + kPoolDxTileRows < N ? r0 + kPoolDxTileRows : N;
+    for (int64_t r = r0 + w; r < r1; r += 4) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            f32x4 v = g[c];
+            if constexpr (kMax) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = sel[c][e] == (int)r ? g[c][e] : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(out + r * o.ldx + (64 * c + lane) * 4) = v;
+        }
+    }
+}
+
+// out[512 b + d, :] = row idx[b][d] of bag b, widened to fp32: one wave per output row.  An index outside the bag (never written by
+// k_colmax_idx_merge) gives a row of zeros instead of a read outside the bag.
+template <typename XT>
+__global__ __launch_bounds__(256) void k_gather_rows(const vlsa_bag_desc* __restrict__ bags, int B, const int* __restrict__ idx,
+                                                      float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * 512) return;
+    const vlsa_bag_desc d = bags[row >> 9];
+    const int n = idx[row];
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (n >= 0 && (int64_t)n < d.N) load_row_512<XT>(static_cast<const XT*>(d.X) + (int64_t)n * d.ldx, lane, v);
+    float* o = out + (size_t)row * 512;
+    if constexpr (sizeof(XT) == 2) {
+        *reinterpret_cast<f32x4*>(o + lane * 8) = f32x4{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(o + lane * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    } else {
+        *reinterpret_cast<f32x4*>(o + lane * 4) = f32x4{v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(o + (64 + lane) * 4) = f32x4{v[4], v[5], v[6], v[7]};
+    }
+}
 }  // namespace vlsa
 
 using namespace vlsa;
@@ -994,6 +1165,58 @@ extern "C" int vlsa_colmax(const void* X, int x_dtype, int64_t N, int64_t ldx, i
     if (x_dtype == VLSA_DT_F32) return launch_colmax<float>((const float*)X, N, ldx, D, partials, out, G, (hipStream_t)stream);
     if (x_dtype == VLSA_DT_BF16) return launch_colmax<__bf16>((const __bf16*)X, N, ldx, D, partials, out, G, (hipStream_t)stream);
     return VLSA_EINVAL;
+}
+
+// ---- MaxMIL / MeanMIL over a bag table (k_colmax_idx_partial .. k_gather_rows) -----------------------------------------------------
+extern "C" int vlsa_colmax_part_rows(void) { return kColmaxPartRows; }
+
+extern "C" int vlsa_colmax_parts(int64_t N) {
+    const int64_t g = (N + kColmaxPartRows - 1) / kColmaxPartRows;
+    return (int)(g < 1 ? 1 : (g > kColmaxMaxParts ? kColmaxMaxParts : g));
+}
+
+extern "C" size_t vlsa_colmax_workspace_bytes(int n_parts) {
+    return (size_t)(n_parts < 1 ? 1 : n_parts) * 512 * (sizeof(float) + sizeof(int));
+}
+
+extern "C" int vlsa_pool_dx_tile_rows(void) { return kPoolDxTileRows; }
+
+static int pool_table_check(int D, int x_dtype) {
+    return (D != 512 || (x_dtype != VLSA_DT_BF16 && x_dtype != VLSA_DT_F32)) ? VLSA_EUNSUPPORTED : VLSA_OK;
+}
+
+extern "C" int vlsa_colmax_batch(const void* bag_desc, int B, int x_dtype, int D, const int* part_start, int n_parts, void* workspace,
+                                 float* out, int* idx, void* stream) {
+    if (!bag_table_ok(bag_desc, B, part_start, n_parts) || !workspace || !out || !idx) return VLSA_EINVAL;
+    if (pool_table_check(D, x_dtype) != VLSA_OK) return VLSA_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    float* pval = static_cast<float*>(workspace);
+    int* pidx = reinterpret_cast<int*>(pval + (size_t)n_parts * 512);
+    if (x_dtype == VLSA_DT_F32) hipLaunchKernelGGL(k_colmax_idx_partial<float>, dim3(n_parts), dim3(256), 0, s, bags, B, part_start, pval, pidx);
+    else hipLaunchKernelGGL(k_colmax_idx_partial<__bf16>, dim3(n_parts), dim3(256), 0, s, bags, B, part_start, pval, pidx);
+    hipLaunchKernelGGL(k_colmax_idx_merge, dim3(4, B), dim3(512), 0, s, part_start, pval, pidx, out, idx);
+    return launch_status();
+}
+
+extern "C" int vlsa_pool_dx_batch(const void* dx_desc, const void* bag_desc, int B, int mode, const int* idx, const float* dpooled,
+                                  const int* tile_start, int n_tiles, void* stream) {
+    if (!bag_table_ok(bag_desc, B, tile_start, n_tiles) || !dx_desc || !dpooled || (mode != 0 && mode != 1) || (mode == 1 && !idx))
+        return VLSA_EINVAL;
+    const vlsa_bag_desc* dx = static_cast<const vlsa_bag_desc*>(dx_desc);
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    if (mode == 1) hipLaunchKernelGGL(k_pool_dx<true>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, dx, bags, B, tile_start, idx, dpooled);
+    else hipLaunchKernelGGL(k_pool_dx<false>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, dx, bags, B, tile_start, idx, dpooled);
+    return launch_status();
+}
+
+extern "C" int vlsa_gather_rows_batch(const void* bag_desc, int B, int x_dtype, const int* idx, float* out, void* stream) {
+    if (!bag_desc || !idx || !out || B < 1 || B > 64) return VLSA_EINVAL;
+    if (pool_table_check(512, x_dtype) != VLSA_OK) return VLSA_EUNSUPPORTED;
+    const vlsa_bag_desc* bags = static_cast<const vlsa_bag_desc*>(bag_desc);
+    if (x_dtype == VLSA_DT_F32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(B * 128), dim3(256), 0, (hipStream_t)stream, bags, B, idx, out);
+    else hipLaunchKernelGGL(k_gather_rows<__bf16>, dim3(B * 128), dim3(256), 0, (hipStream_t)stream, bags, B, idx, out);
+    return launch_status();
 }
 
 extern "C" int vlsa_attn_scores(const float* H, const float* Hg, int64_t N, int hid, const float* b1, const float* bg,

@@ -321,6 +321,21 @@ class VLFAN(VF.nat.TransientCaches, nn.Module):
         return (outs[0] if len(outs) == 1 else torch.cat(outs)), attn
 
 
+def _batch_pools(flat) -> bool:
+    """whether the batched max / mean pooling takes these [N_i, C] bags: device tensors of width 512 and one dtype (bf16 or fp32), none empty"""
+    return (len(flat) > 0 and flat[0].dtype in (torch.bfloat16, torch.float32)
+            and all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == flat[0].dtype for x in flat))
+
+
+def _pool_chunks(flat, pool):
+    """``pool`` (VF.max_pool_bags / VF.mean_pool_bags) over the bags in chunks of 64; a ``BagSet`` or the projected bags of one chunk go
+    in as they are, with their device-side table"""
+    if len(flat) <= 64:
+        return pool(flat)
+    is_set = isinstance(flat, VF.BagSet)
+    return torch.cat([pool(flat.chunk(i, 64) if is_set else flat[i:i + 64]) for i in range(0, len(flat), 64)])
+
+
 class DeepMIL(VF.nat.TransientCaches, nn.Module):
     """ABMIL-style encoder (model/deepmil.py:222-292): optional Feat_Projecter, mean / max / (gated-)attention pooling
     over the N patches, Adapter head mixed with ``keep_ratio`` or a Linear head."""
@@ -356,6 +371,8 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             if sg == "mean" and len(flat) > 0 and all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0
                                                       and x.dtype == flat[0].dtype for x in flat):
                 return torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
+            if sg == "max" and len(flat) > 1 and _batch_pools(flat):
+                return _pool_chunks(flat, VF.max_pool_bags)
             return torch.stack([VF.scored_pool(x, None) if sg == "mean" else VF.colmax(x) for x in flat])
         gated = isinstance(sg, Gated_Attention_Pooling)
         lin_a = sg.fc1[0] if gated else sg.attention[0]
@@ -431,24 +448,37 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
         ``forward(x, ret_with_attn=True)`` hands it out (raw scores for Attention_Pooling, softmax weights for the gated module).
         (Gated) attention pooling with 512 -> 256 hidden units runs as one autograd node per <= 64 bags
         (VF.attn_pool_bags_autograd: three launches forward, one backward pass + reductions, dropout seeds from a device counter);
-        mean / max pooling as batched launches.  ``projected``: the bags already went through ``feat_proj``."""
+        mean / max pooling as batched launches -- under a bag gradient (a trainable projecter in front) as one node per <= 64 bags
+        (VF.mean_pool_bags / VF.max_pool_bags: the row gradients of all bags in one launch), and max pooling behind a trainable
+        projecter that this call runs itself as projecter + max in one node over the selected rows (VF.project_max_pool_bags).  The
+        batched max follows the reference's ``torch.max``: where a column's maximum is tied, its gradient goes to the first maximal
+        row (the per-bag ``forward`` splits it, ``amax``).  ``projected``: the bags already went through ``feat_proj``."""
         flat = bags if isinstance(bags, VF.BagSet) else [VF._bag2d(x) for x in bags]
-        if self.feat_proj is not None and not projected:
+        sg = self.sigma
+        f = None
+        if (sg == "max" and self.feat_proj is not None and not projected and self.feat_proj.trains()
+                and self.feat_proj.serves_batch(flat)):
+            # a trainable projecter in front of the max: projecter and pooling as one node that keeps the selected rows only
+            f = self.feat_proj.max_pool_bags(flat)
+        elif self.feat_proj is not None and not projected:
             flat = self.feat_proj.forward_bags(flat)          # fp32 [N, 512]; a trainable projecter gets dX from the pooling
         if len(flat) == 0:
             raise ValueError("forward_bags needs at least one bag")
         bag_grad = torch.is_grad_enabled() and any(x.requires_grad for x in flat)
-        uniform = (all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == flat[0].dtype for x in flat)
-                   and flat[0].dtype in (torch.bfloat16, torch.float32))
+        uniform = _batch_pools(flat)
         attn = None
-        sg = self.sigma
-        if sg == "mean":
-            if uniform and not bag_grad:
-                f = torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
+        if f is not None:
+            pass
+        elif sg == "mean":
+            if uniform:
+                f = _pool_chunks(flat, VF.mean_pool_bags)     # with a bag gradient: one node per chunk, dX of all bags in one launch
             else:
                 f = torch.stack([x.float().mean(dim=0) if (bag_grad or not x.is_cuda) else VF.scored_pool(x, None) for x in flat])
         elif sg == "max":
-            f = torch.stack([x.float().amax(dim=0) if (bag_grad or not x.is_cuda) else VF.colmax(x) for x in flat])
+            if uniform and (bag_grad or len(flat) > 1):
+                f = _pool_chunks(flat, VF.max_pool_bags)
+            else:                                             # one bag per call without a gradient: the single-bag launch pair
+                f = torch.stack([x.float().amax(dim=0) if (bag_grad or not x.is_cuda) else VF.colmax(x) for x in flat])
         else:
             gated = isinstance(sg, Gated_Attention_Pooling)
             lin_a, lin_g, lin_o, drop_a, drop_g = self._pool_modules()

@@ -1465,11 +1465,108 @@ def attn_pool_bags_autograd(bags, fused: "FusedAttnScores", Wa, ba, Wg, bg, w2, 
     return _AttnPoolBagsFn.apply(plan, prep, prep_t, Wa, ba, Wg, bg, w2, c, drop_p, seed_word if drop_p else None, *bags)
 
 
+class PoolBagsPlan(_ChunkPlan):
+    """Tables of one chunk of <= 64 bags for the batched max / mean pooling (vlsa_colmax_batch, vlsa_pool_dx_batch): the descriptor
+    table, part_start of the column max (``vlsa_colmax_parts(N_b)`` parts per bag) and tile_start of the dense row gradient -- from
+    a ``BagSet`` or the projected bags of one (``ProjectedBags``) derived on the device by in-stream ops, so nothing is staged and the
+    route can be captured; a plain list has its descriptor staged first."""
+
+    def __init__(self, bags):
+        lib = nat.load()
+        super().__init__(_chunk_tables(bags, "the batched max / mean pooling over a plain list of bags"))
+        self.part_table(lib.vlsa_colmax_part_rows, lib.vlsa_colmax_parts)
+        self.dx_rows = int(lib.vlsa_pool_dx_tile_rows())
+        self.tables.tile_start(self.dx_rows)        # the backward's: derived with the plan, not inside a backward pass
+
+
+def _colmax_launch(desc: torch.Tensor, B: int, dt: int, part_start: torch.Tensor, n_parts: int):
+    """(out [B, 512] fp32, idx [B, 512] int32: the first maximal row of every column, within its bag) -- two launches"""
+    lib, dev = nat.load(), desc.device
+    ws = torch.empty(lib.vlsa_colmax_workspace_bytes(n_parts), dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 512, dtype=torch.float32, device=dev)
+    idx = torch.empty(B, 512, dtype=torch.int32, device=dev)
+    nat.check(lib.vlsa_colmax_batch(_p(desc), B, dt, 512, _p(part_start), n_parts, _p(ws), _p(out), _p(idx), _stream()), "vlsa_colmax_batch")
+    return out, idx
+
+
+def gather_rows_bags(desc: torch.Tensor, B: int, dt: int, idx: torch.Tensor) -> torch.Tensor:
+    """fp32 [B * 512, 512]: row 512 b + d is row idx[b, d] of bag b of the table (bf16 widened exactly) -- one launch"""
+    out = torch.empty(B * 512, 512, dtype=torch.float32, device=desc.device)
+    nat.check(nat.load().vlsa_gather_rows_batch(_p(desc), B, dt, _p(idx), _p(out), _stream()), "vlsa_gather_rows_batch")
+    return out
+
+
+class _PoolBagsFn(torch.autograd.Function):
+    """Max (mode 1) or mean (mode 0) pooling [B, 512] of a chunk of <= 64 bags that carry a gradient as ONE autograd node.  Forward:
+    vlsa_colmax_batch (the row of every maximum is kept) / the pooling partials and their merge (``pool_rows``).  Backward: ONE
+    vlsa_pool_dx_batch into ONE packed fp32 [sum N_i, 512] buffer; the per-bag gradients are its views, which is what the batched
+    projecter's backward looks for.  The max follows torch.max: the gradient goes to the FIRST maximal row.  Returns (pooled, idx);
+    idx (None for the mean) is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, plan, mode, *bag_tensors):
+        if mode == 1:
+            pooled, idx = _colmax_launch(plan.desc, plan.B, plan.dt, plan.part_start, plan.n_parts)
+            ctx.save_for_backward(idx)
+            ctx.mark_non_differentiable(idx)
+        else:
+            pooled, idx = pool_rows(plan.desc, plan.B, plan.dt, None, None)[0], None
+        ctx.plan, ctx.mode = plan, mode
+        ctx.bag_dtypes = [x.dtype for x in bag_tensors]
+        ctx.bags = bag_tensors                        # the descriptor table holds their addresses
+        return pooled, idx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dpooled, _didx):
+        plan, mode = ctx.plan, ctx.mode
+        idx = ctx.saved_tensors[0] if mode == 1 else None
+        dp = _f32c(dpooled)
+        dX = torch.empty(plan.total, 512, dtype=torch.float32, device=dp.device)
+        dx_desc = plan.tables.packed_desc(dX.data_ptr())
+        ts, n_tiles = plan.tables.p_tile_start(plan.dx_rows)
+        nat.check(nat.load().vlsa_pool_dx_batch(_p(dx_desc), _p(plan.desc), plan.B, mode, _p(idx), _p(dp), ts, n_tiles, _stream()),
+                  "vlsa_pool_dx_batch")
+        dxs = [None] * plan.B
+        for i in range(plan.B):
+            if ctx.needs_input_grad[2 + i]:
+                g = dX[plan.offs[i]:plan.offs[i + 1]]
+                dxs[i] = g if ctx.bag_dtypes[i] == torch.float32 else g.to(ctx.bag_dtypes[i])
+        return (None, None, *dxs)
+
+
+def _bag_grad(bags) -> bool:
+    return torch.is_grad_enabled() and any(x.requires_grad for x in bags)
+
+
+def max_pool_bags(bags, return_index: bool = False):
+    """Column maxima [B, 512] fp32 of a chunk of 1..64 validated [N_i, 512] device bags (one dtype, N_i >= 1, 16-byte aligned rows; a
+    ``BagSet`` or ``ProjectedBags`` brings its table) in two launches -- the 'max' pooling of FeatMIL / DeepMIL over a batch
+    (model/deepmil.py:59-60,273-274 per bag).  ``return_index``: also idx [B, 512] int32, the row within its bag every maximum came
+    from: the FIRST maximal row, as ``torch.max(X, dim=1)`` names it.  A bag's result is the same alone and in any batch.  With grad
+    enabled and a bag that requires grad the chunk is ONE autograd node (_PoolBagsFn) whose backward writes the row gradients of all
+    bags in one launch (to the first maximal row: where a column's maximum is tied this differs from ``amax``, which splits it)."""
+    _chunk_len(bags)
+    _need_gpu(bags[0])
+    plan = PoolBagsPlan.of(bags)
+    if _bag_grad(bags):
+        out, idx = _PoolBagsFn.apply(plan, 1, *bags)
+    else:
+        out, idx = _colmax_launch(plan.desc, plan.B, plan.dt, plan.part_start, plan.n_parts)
+    return (out, idx) if return_index else out
+
+
 def mean_pool_bags(bags) -> torch.Tensor:
     """Row means [B, 512] of up to 64 validated [N_i, 512] device bags (one dtype) in two launches (the 'mean' pooling of
-    FeatMIL / DeepMIL over a batch: model/deepmil.py:57-58,271-272 per bag)."""
+    FeatMIL / DeepMIL over a batch: model/deepmil.py:57-58,271-272 per bag).  A ``BagSet`` or ``ProjectedBags`` brings its descriptor
+    table: nothing is staged.  With grad enabled and a bag that requires grad: ONE autograd node (_PoolBagsFn, mode 0) with the same
+    forward, whose backward writes dpooled[b] / N_b into every row of all bags in one launch."""
     B = _chunk_len(bags)
-    desc = _stage_table(bag_rows(bags), bags[0].device, "mean_pool_bags")
+    if _bag_grad(bags):
+        return _PoolBagsFn.apply(PoolBagsPlan.of(bags), 0, *bags)[0]
+    desc = bags.desc() if isinstance(bags, (BagSet, ProjectedBags)) else None
+    if desc is None:
+        desc = _stage_table(bag_rows(bags), bags[0].device, "mean_pool_bags")
     return pool_rows(desc, B, _dt(bags[0]), None, None)[0]
 
 
@@ -1675,6 +1772,71 @@ def feat_project_bags(bags, fused: "FusedFeatProjecter", W, b, gamma, beta, eps:
         return ProjectedBags(_FeatProjectBagsFn.apply(plan, prep, W, b, gamma, beta, float(eps)), plan)
     Y, _ = _feat_project_bags_launch(plan, prep, eps, False)
     return ProjectedBags(Y.split(plan.sizes), plan)
+
+
+class _ProjectMaxPoolFn(torch.autograd.Function):
+    """Feat_Projecter then max pooling of a chunk of <= 64 bags as ONE autograd node, for a trainable projecter.  The max touches at
+    most 512 rows of a bag, so only those are kept: forward = the batched projecter launch (training statistics), vlsa_colmax_batch
+    over the packed Y, then the gather of the selected input rows Xsel (vlsa_gather_rows_batch), output rows Ysel and LayerNorm
+    statistics -- the packed Y and stats are dropped on return.  Backward = the EXISTING row-statistics and weight-gradient kernels
+    over a table of B bags of 512 fp32 rows, with dYsel[512 b + d] = dpooled[b][d] e_d.  A row chosen by several columns appears
+    several times; LayerNorm's backward is linear in dY per row, so the sum over its copies is exact."""
+
+    @staticmethod
+    def forward(ctx, plan, prep, W, b, gamma, beta, eps):
+        B = plan.B
+        Y, stats = _feat_project_bags_launch(plan, prep, eps, True)
+        if not hasattr(plan, "part_start"):
+            lib = nat.load()
+            plan.part_table(lib.vlsa_colmax_part_rows, lib.vlsa_colmax_parts)
+        pooled, idx = _colmax_launch(plan.tables.packed_desc(Y.data_ptr()), B, nat.DT_F32, plan.part_start, plan.n_parts)
+        rows = (plan.tables.row_off[:, None] + idx).reshape(-1)
+        sel_stats = torch.zeros(B * 512, 4, dtype=torch.float32, device=Y.device)
+        sel_stats[:, :2] = stats.index_select(0, rows)[:, :2]
+        ctx.save_for_backward(gather_rows_bags(plan.desc, B, plan.dt, idx), Y.index_select(0, rows), sel_stats, prep)
+        ctx.B = B
+        ctx.has = (b is not None, gamma is not None, beta is not None)
+        return pooled
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dpooled):
+        lib, s = nat.load(), _stream()
+        Xsel, Ysel, stats, prep = ctx.saved_tensors
+        dev, B = Xsel.device, ctx.B
+        dY = torch.diag_embed(_f32c(dpooled)).reshape(B * 512, 512)
+        n = torch.full((B,), 512, dtype=torch.int64, device=dev)
+        first = torch.arange(B, dtype=torch.int64, device=dev) * (512 * 2048)
+        t = ChunkTables.from_device(torch.stack([first + Xsel.data_ptr(), n, n], 1).contiguous(), [512] * B, nat.DT_F32)
+        dy_desc = t.packed_desc(dY.data_ptr())
+        tile_rows = int(lib.vlsa_mlp_bwd_tile_rows(nat.DT_F32))
+        ts, n_tiles = t.p_tile_start(tile_rows)
+        nat.check(lib.vlsa_feat_project_rowstats_batch(_p(dy_desc), B, _p(Ysel), t.p_row_off, B * 512, _p(prep), _p(stats), s),
+                  "vlsa_feat_project_rowstats_batch")
+        ws = torch.empty(lib.vlsa_mlp_bwd_workspace_bytes(2, n_tiles), dtype=torch.uint8, device=dev)
+        dW = torch.empty(512, 512, dtype=torch.float32, device=dev)
+        dvec = torch.empty(3, 512, dtype=torch.float32, device=dev)
+        nat.check(lib.vlsa_feat_project_backward(t.p_desc, _p(dy_desc), B, nat.DT_F32, _p(prep), ts, n_tiles, _p(stats), t.p_row_off, _p(ws),
+                                                 _p(dW), _p(dvec), s), "vlsa_feat_project_backward")
+        hb, hg, hbt = ctx.has
+        return None, None, dW, dvec[0] if hb else None, dvec[1] if hg else None, dvec[2] if hbt else None, None
+
+
+def project_max_pool_bags(bags, fused: "FusedFeatProjecter", W, b, gamma, beta, eps: float) -> torch.Tensor:
+    """max over the rows of Feat_Projecter(bag) [B, 512] fp32 for a chunk of 1..64 bags (as ``feat_project_bags`` takes them: a
+    ``BagSet`` or validated tensors without a gradient of their own) with a TRAINABLE projecter, as ONE autograd node
+    (_ProjectMaxPoolFn): equal to ``max_pool_bags(feat_project_bags(...))`` in the forward, while the backward runs over the <= 512
+    selected rows of each bag instead of all of them and no [sum N_i, 512] tensor outlives the call.  Without grad, or with a
+    frozen projecter, it is that composition."""
+    _chunk_len(bags)
+    _need_gpu(bags[0])
+    if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (W, b, gamma, beta))):
+        return max_pool_bags(feat_project_bags(bags, fused, W, b, gamma, beta, eps))
+    _no_bag_grad(*bags)
+    if torch.cuda.is_current_stream_capturing():
+        fused = FusedFeatProjecter()
+    prep = fused.packed(bags[0].device, W, b, gamma, beta)
+    return _ProjectMaxPoolFn.apply(FeatProjBagsPlan.of(bags), prep, W, b, gamma, beta, float(eps))
 
 
 def topk_mean(S: torch.Tensor, k: int, out_scale: float = 1.0) -> torch.Tensor:

@@ -60,6 +60,21 @@ class Feat_Projecter(_TransientCaches, nn.Module):
             return self.projecter(x.reshape(-1, d)).reshape(b, n, -1)
         return self.projecter(x)
 
+    def serves_batch(self, bags) -> bool:
+        """whether the batch kernel (vlsa_feat_project_batch) takes these bags behind this projecter: device tensors of one dtype
+        (bf16 or fp32) and width 512 without a gradient of their own, no empty bag, Linear(512, 512) + affine LayerNorm(512)"""
+        from . import functional as VF
+        lin, norm = self.projecter[0], self.projecter[1]
+        is_set = isinstance(bags, VF.BagSet)
+        grad = torch.is_grad_enabled()
+
+        def takes(x):
+            return (x.is_cuda and (x.dim() == 2 or (x.dim() == 3 and x.shape[0] == 1)) and x.shape[-1] == 512 and x.shape[-2] > 0
+                    and x.dtype == bags[0].dtype and x.device == bags[0].device and not (grad and x.requires_grad))
+        return (len(bags) > 0 and lin.in_features == 512 and lin.out_features == 512 and tuple(norm.normalized_shape) == (512,)
+                and norm.elementwise_affine and lin.weight.is_cuda and bags[0].dtype in (torch.bfloat16, torch.float32)
+                and ((is_set and bags.D == 512) or all(takes(x) for x in bags)))
+
     def forward_bags(self, bags):
         """``[self(x) for x in bags]`` for a list (or ``BagSet``) of bags, each [N_i, 512] or [1, N_i, 512]: ONE fused HIP launch per
         chunk of 64 bags into one packed fp32 allocation (vlsa_feat_project_batch; the results are its per-bag views, bit-equal to
@@ -69,14 +84,7 @@ class Feat_Projecter(_TransientCaches, nn.Module):
         from . import functional as VF
         lin, norm = self.projecter[0], self.projecter[1]
         is_set = isinstance(bags, VF.BagSet)
-        grad = torch.is_grad_enabled()
-
-        def takes(x):
-            return (x.is_cuda and (x.dim() == 2 or (x.dim() == 3 and x.shape[0] == 1)) and x.shape[-1] == 512 and x.shape[-2] > 0
-                    and x.dtype == bags[0].dtype and x.device == bags[0].device and not (grad and x.requires_grad))
-        if not (len(bags) > 0 and lin.in_features == 512 and lin.out_features == 512 and tuple(norm.normalized_shape) == (512,)
-                and norm.elementwise_affine and lin.weight.is_cuda and bags[0].dtype in (torch.bfloat16, torch.float32)
-                and ((is_set and bags.D == 512) or all(takes(x) for x in bags))):
+        if not self.serves_batch(bags):
             return [self.forward(x) for x in bags]
         if not hasattr(self, "_fused"):
             self._fused = VF.FusedFeatProjecter()
@@ -87,6 +95,25 @@ class Feat_Projecter(_TransientCaches, nn.Module):
             chunk = bags.chunk(i, 64) if is_set else [VF._bag2d(x) for x in bags[i:i + 64]]
             out.extend(self._fused.forward_bags(chunk, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps))
         return out if is_set else [y if x.dim() == 2 else y[None] for x, y in zip(bags, out)]
+
+
+    def trains(self) -> bool:
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def max_pool_bags(self, bags):
+        """max over the rows of ``self(x)`` for every bag, [B, 512] fp32, for bags ``serves_batch`` takes and a projecter that
+        trains: ONE autograd node per chunk of 64 bags whose backward runs over the <= 512 selected rows of each bag
+        (VF.project_max_pool_bags)"""
+        from . import functional as VF
+        lin, norm = self.projecter[0], self.projecter[1]
+        if not hasattr(self, "_fused"):
+            self._fused = VF.FusedFeatProjecter()
+        is_set = isinstance(bags, VF.BagSet)
+        out = []
+        for i in range(0, len(bags), 64):
+            chunk = bags.chunk(i, 64) if is_set else [VF._bag2d(x) for x in bags[i:i + 64]]
+            out.append(VF.project_max_pool_bags(chunk, self._fused, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps))
+        return out[0] if len(out) == 1 else torch.cat(out)
 
 
 def _note(module, x):

@@ -1019,10 +1019,13 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             if same and isinstance(enc, FeatMIL) and enc.pooling not in ("mean", "max") and text_features.shape[0] <= 64:
                 return self._forward_bags_zeroshot(flat, text_features)
             if same and isinstance(enc, FeatMIL) and enc.pooling in ("mean", "max"):
-                # FeatMIL baseline (model/deepmil.py:57-60): row means of all bags in two launches / column maxima bag by bag,
-                # then normalise + cosine logits on [B, 512]
+                # FeatMIL baseline (model/deepmil.py:57-60): row means / column maxima of all bags in two launches per 64 bags
+                # (one bag per call: the single-bag launch pair), then normalise + cosine logits on [B, 512]
                 if enc.pooling == "mean":
                     f = torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
+                elif len(flat) > 1:
+                    f = torch.cat([VF.max_pool_bags(bagset.chunk(i, 64) if bagset is not None else flat[i:i + 64])
+                                   for i in range(0, len(flat), 64)])
                 else:
                     f = torch.stack([VF.colmax(x) for x in flat])
                 That = F.normalize(text_features.detach().float(), dim=-1)
