@@ -485,7 +485,9 @@ int vlsa_scored_pool_backward(const void* X, int x_dtype, int64_t N, int64_t ldx
  */
 int vlsa_topk_mean(const float* S, int C, int64_t N, int k, float out_scale, float* out, void* stream);
 /* Same in two stages for long rows (N / 4096 chunks per class in parallel, then a merge of the chunk winners): what the
- * zero-shot path uses.  workspace: vlsa_topk_workspace_bytes(C, N, k), no initialisation needed. */
+ * zero-shot path uses.  workspace: vlsa_topk_workspace_bytes(C, N, k), no initialisation needed.
+ * vlsa_topk_chunks(N) = clamp(ceil(N / 4096), 1, 128): the chunks per class, one candidate list of min(k, 32) floats each. */
+int vlsa_topk_chunks(int64_t N);
 size_t vlsa_topk_workspace_bytes(int C, int64_t N, int k);
 int vlsa_topk_mean_ws(const float* S, int C, int64_t N, int k, float out_scale, void* workspace, float* out, void* stream);
 

@@ -4,7 +4,6 @@ host-side argument checks, the refusal of DSMIL as a VLSA image encoder and of C
 import ctypes
 import glob
 import os
-import re
 import sys
 import types
 
@@ -13,6 +12,7 @@ import pytest
 import torch
 
 import dsmil_cases as DC
+from abi_helpers import declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vlsa_dsmil_parts", "vlsa_dsmil_workspace_bytes", "vlsa_dsmil_state_floats", "vlsa_dsmil_forward_batch", "vlsa_dsmil_backward_batch")
@@ -135,8 +135,7 @@ def lib():
 
 def test_new_symbols_exported_declared_and_bound(lib):
     from vlsa_amd import _native
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vlsa_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(vlsa_[a-z0-9_]+)\s*\(", txt))
+    declared = set(declared_symbols())
     assert declared == set(_native.exported_symbols())           # header == bindings still holds
     for name in NEW:
         assert hasattr(lib, name) and name in declared

@@ -2,12 +2,12 @@
 vlsa_feat_project_rowstats_batch): exported, declared in the header and bound, and they refuse bad arguments on the host with the
 stated codes -- before anything is launched, so no GPU is needed."""
 import ctypes
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import HEADER_TEXT
+
 NEW = ("vlsa_feat_project_batch", "vlsa_feat_project_batch_tile_rows", "vlsa_feat_project_rowstats_batch")
 EINVAL, EUNSUPPORTED = -1, -2          # include/vlsa_hip.h
 BF16, F32 = 1, 0
@@ -23,10 +23,9 @@ def lib():
 def test_new_symbols_exported_declared_and_bound(lib):
     from vlsa_amd import _native
     assert (_native.DT_BF16, _native.DT_F32) == (BF16, F32)
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vlsa_hip.h")).read(), flags=re.S)
     for name in NEW:
         assert hasattr(lib, name)
-        assert re.search(r"\b" + name + r"\s*\(", txt), f"{name} not declared in include/vlsa_hip.h"
+        assert re.search(r"\b" + name + r"\s*\(", HEADER_TEXT), f"{name} not declared in include/vlsa_hip.h"
         assert name in _native.exported_symbols()
     assert lib.vlsa_abi_version() == 1
 

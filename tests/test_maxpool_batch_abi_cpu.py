@@ -2,12 +2,12 @@
 their host-side queries): exported, declared in the header and bound, they refuse bad arguments on the host -- before anything is
 launched, so no GPU is needed -- and a bag's part count is a function of its row count alone."""
 import ctypes
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_helpers import HEADER_TEXT
+
 NEW = ("vlsa_colmax_part_rows", "vlsa_colmax_parts", "vlsa_colmax_workspace_bytes", "vlsa_colmax_batch", "vlsa_pool_dx_tile_rows",
        "vlsa_pool_dx_batch", "vlsa_gather_rows_batch")
 
@@ -21,10 +21,9 @@ def lib():
 
 def test_new_symbols_exported_declared_and_bound(lib):
     from vlsa_amd import _native
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vlsa_hip.h")).read(), flags=re.S)
     for name in NEW:
         assert hasattr(lib, name)
-        assert re.search(r"\b" + name + r"\s*\(", txt), f"{name} not declared in include/vlsa_hip.h"
+        assert re.search(r"\b" + name + r"\s*\(", HEADER_TEXT), f"{name} not declared in include/vlsa_hip.h"
         assert name in _native.exported_symbols()
     assert lib.vlsa_abi_version() == 1
 

@@ -2,7 +2,6 @@
 GPU: its three entry points are declared and bound, the closed-form gradient its backward kernel implements equals the oracle's
 autograd gradient in float64, and every case of the GPU suite meets the selection-gap precondition."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -10,19 +9,17 @@ import pytest
 import torch
 
 import cases
+from abi_helpers import HEADER_TEXT
 import zeroshot_train_cases as Z
 from oracle import vlsa_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("vlsa_topk_select_batch", "vlsa_unit_mean_batch", "vlsa_zeroshot_backward_batch")
 
 
 def test_the_three_entry_points_are_declared_and_bound():
     from vlsa_amd import _native
-    txt = open(os.path.join(ROOT, "include", "vlsa_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     for name in SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", txt), f"{name} is not declared in include/vlsa_hip.h"
+        assert re.search(r"\bint\s+" + name + r"\s*\(", HEADER_TEXT), f"{name} is not declared in include/vlsa_hip.h"
         assert name in _native.exported_symbols(), f"{name} is not bound in vlsa_amd/_native.py"
     assert _native._SIGNATURES["vlsa_topk_select_batch"][1][:-2] == _native._SIGNATURES["vlsa_topk_mean_batch"][1][:-1]
 

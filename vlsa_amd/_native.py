@@ -8,232 +8,108 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_ubyte, c_uint32, c_void_p
 
-_LIB_PATH = os.environ.get("VLSA_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib",
-                                                             "libvlsa_hip.so")
-ABI_VERSION = 1
-
-# mirrors include/vlsa_hip.h
-DT_F32, DT_BF16 = 0, 1
-KERNEL_AUTO, KERNEL_GENERIC, KERNEL_MFMA, KERNEL_DMA = 0, 1, 2, 3
-POOL_MEAN, POOL_MAX, POOL_WEIGHT, POOL_GIVEN = 0, 1, 2, 3
-MAX_P, MAX_K, MAX_D = 16, 64, 1024
-TT_PERSISTENT = 0x100      # vlsa_tt_forward: or-ed into save_for_backward (VLSA_TT_PERSISTENT)
-P_STRIDE = 16
-
-
-ADAM_MAX_TENSORS = 16
-
-
-class AdamTensor(ctypes.Structure):        # vlsa_adam_tensor
-    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("n", c_int64), ("hyper", c_int)]
+_PKG = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.environ.get("VLSA_HIP_LIB") or os.path.join(_PKG, "_lib", "libvlsa_hip.so")
+_HEADER_PATH = os.path.normpath(os.path.join(_PKG, "..", "include", "vlsa_hip.h"))     # the file every .hip source is compiled against
 
 
 class VlsaNativeError(RuntimeError):
     pass
 
 
-_SIGNATURES = {
-    "vlsa_abi_version": (c_int, []),
-    "vlsa_error_string": (c_char_p, [c_int]),
-    "vlsa_num_partials": (c_int, [c_int64]),
-    "vlsa_qprep_bytes": (c_size_t, [c_int]),
-    "vlsa_qprep_qeff": (c_void_p, [c_void_p, c_int]),
-    "vlsa_qprep_qhat": (c_void_p, [c_void_p, c_int]),
-    "vlsa_qprep_qnorm": (c_void_p, [c_void_p, c_int]),
-    "vlsa_prepare_queries": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "vlsa_prepare_queries_and_text": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
-                                              c_void_p, c_void_p, c_void_p]),
-    "vlsa_vlfan_partial": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_int,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_vlfan_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                 c_void_p, c_void_p]),
-    "vlsa_vlfan_merge_strided": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
-                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_bwd_prep_bytes": (c_size_t, [c_int]),
-    "vlsa_vlfan_backward": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_float, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_attn_normalise": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_normalize_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_head_workspace_bytes": (c_size_t, [c_int]),
-    "vlsa_vlfan_merge_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int]
-                              + [c_void_p] * 12),
-    "vlsa_head_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p]),
-    "vlsa_vlfan_forward_bag": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int,
-                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] + [c_void_p] * 13),
-    "vlsa_fill_one_bag_tables": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p]),
-    "vlsa_vlfan_backward_bag": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_float] + [c_void_p] * 14 + [c_int]
-                                + [c_void_p] * 10 + [c_int] + [c_void_p] * 3),
-    "vlsa_batch_max_bags": (c_int, []),
-    "vlsa_batch_forward_max_bags": (c_int, []),
-    "vlsa_batch_partials_per_bag": (c_int, [c_int]),
-    "vlsa_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "vlsa_vlfan_partial_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "vlsa_batch_groups": (c_int, [c_void_p, c_int, c_int]),
-    "vlsa_batch_partials_per_bag_ex": (c_int, [c_int, c_int, c_int]),
-    "vlsa_vlfan_partial_batch_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "vlsa_vlfan_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "vlsa_vlfan_partial_batch_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                                c_void_p]),
-    "vlsa_attn_normalise_batch": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_vlfan_forward_batch_attn": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                              c_void_p, c_int64, c_void_p]),
-    "vlsa_bwd_batch_partials": (c_int, []),
-    "vlsa_vlfan_backward_bags": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "vlsa_bwd_batch_prep_bytes": (c_size_t, [c_int, c_int]),
-    "vlsa_vlfan_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "vlsa_vlfan_merge_batch_strided": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                               c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_vlfan_merge_head_batch_strided": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
-                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_head_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p]),
-    "vlsa_pack_rows_bf16": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
-    "vlsa_surv_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_int,
-                               c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_surv_objective": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float, c_float, c_int, c_int,
-                                    c_float, c_float, c_void_p, c_void_p, c_void_p]),
-    "vlsa_query_chain": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "vlsa_adam_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
-    "vlsa_gated_prep_bytes": (c_size_t, [c_int]),
-    "vlsa_prepare_gated_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                           c_void_p, c_void_p]),
-    "vlsa_gated_scores": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "vlsa_gated_scores_tiling": (c_int, [c_int, c_int, c_void_p, c_void_p]),
-    "vlsa_gated_scores_big_tile": (c_int, [c_int, c_int, c_void_p, c_void_p]),
-    "vlsa_gated_scores_pool_ws_floats": (c_int64, [c_int64]),
-    "vlsa_gated_scores_pool": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_gated_scores_pool_adapter": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p]),
-    "vlsa_gated_scores_pool_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, c_void_p]),
-    "vlsa_gated_scores_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                        c_int64, c_void_p]),
-    "vlsa_scored_pool_partial_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                               c_void_p, c_void_p]),
-    "vlsa_head_forward_batch_text": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_head_backward_batch": (c_int, [c_void_p] * 11 + [c_int, c_int, c_int, c_int] + [c_void_p] * 7),
-    "vlsa_prompt_sentences": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                      c_int, c_void_p, c_void_p]),
-    "vlsa_prompt_sentences_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                               c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_prototype_shapley": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "vlsa_featproj_prep_bytes": (c_size_t, []),
-    "vlsa_prepare_featproj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "vlsa_feat_project": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
-    "vlsa_adapter_head": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "vlsa_pool_num_partials": (c_int, [c_int64]),
-    "vlsa_scored_pool_partial": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p]),
-    "vlsa_colmax": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_colmax_part_rows": (c_int, []),
-    "vlsa_colmax_parts": (c_int, [c_int64]),
-    "vlsa_colmax_workspace_bytes": (c_size_t, [c_int]),
-    "vlsa_colmax_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_pool_dx_tile_rows": (c_int, []),
-    "vlsa_pool_dx_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "vlsa_gather_rows_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_attn_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p]),
-    "vlsa_query_pool_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_rowdot": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_scored_pool_backward": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p]),
-    "vlsa_topk_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
-    "vlsa_topk_mean_ws": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "vlsa_topk_values": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_topk_mean_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_topk_select_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_unit_mean_workspace_bytes": (c_size_t, [c_int]),
-    "vlsa_unit_mean_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vlsa_zeroshot_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 10),
-    "vlsa_normalize_many": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]),
-    "vlsa_topk_mean": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p]),
-    "vlsa_tt_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int]),
-    "vlsa_tt_status_offset": (c_int64, [c_void_p, c_void_p, c_int]),
-    "vlsa_tt_packed_bytes": (c_size_t, [c_void_p, c_int]),
-    "vlsa_tt_pack_weights": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
-    "vlsa_tt_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
-    "vlsa_tt_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "vlsa_tt_backward_train": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
-                                       c_void_p]),
-    "vlsa_mlp_bwd_tile_rows": (c_int, [c_int]),
-    "vlsa_mlp_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "vlsa_attn_scores_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_float, c_uint32, c_void_p]),
-    "vlsa_attn_dx_prep_bytes": (c_size_t, [c_int]),
-    "vlsa_prepare_attn_dx_weights": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "vlsa_attn_scores_backward_dx": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_float, c_uint32, c_void_p]),
-    "vlsa_gated_scores_batch_train": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                              c_int64, c_float, c_void_p, c_void_p]),
-    "vlsa_attn_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_float, c_void_p, c_void_p]),
-    "vlsa_attn_scores_backward_dx_seeded": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
-    "vlsa_gated_scores_train": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_float, c_uint32, c_void_p]),
-    "vlsa_feat_project_train": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
-    "vlsa_feat_project_rowstats": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "vlsa_feat_project_batch_tile_rows": (c_int, [c_int, c_int64]),
-    "vlsa_feat_project_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                        c_void_p]),
-    "vlsa_feat_project_rowstats_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "vlsa_feat_project_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p]),
-    "vlsa_vlfan_backward_dx": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vlsa_dsmil_part_rows": (c_int, []),
-    "vlsa_dsmil_parts": (c_int, [c_int64]),
-    "vlsa_dsmil_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "vlsa_dsmil_state_floats": (c_size_t, [c_int, c_int, c_void_p]),
-    "vlsa_dsmil_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 8
-                                 + [c_float] + [c_void_p] * 7),
-    "vlsa_dsmil_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4
-                                  + [c_float] + [c_void_p] * 12),
-    "vlsa_cluster_pool_tile_rows": (c_int, []),
-    "vlsa_cluster_pool_parts": (c_int, [c_int64]),
-    "vlsa_cluster_pool_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "vlsa_cluster_pool_backward_tile_rows": (c_int, []),
-    "vlsa_cluster_pool_backward_workspace_bytes": (c_size_t, [c_int]),
-    "vlsa_cluster_pool_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
-    "vlsa_cluster_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 9),
-    "vlsa_ilra_tile_rows": (c_int, []),
-    "vlsa_ilra_pool_part_rows": (c_int, []),
-    "vlsa_ilra_pool_parts": (c_int, [c_int64]),
-    "vlsa_ilra_pool_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "vlsa_ilra_rowmap_backward_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
-    "vlsa_ilra_pool_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 8),
-    "vlsa_ilra_pool_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 11),
-    "vlsa_ilra_rowmap_forward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 11),
-    "vlsa_ilra_rowmap_backward_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64]
-                                        + [c_void_p] * 20),
-    "vlsa_debug_probe": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),
-    "vlsa_xchg_max_peers": (c_int, []),
-    "vlsa_xchg_result_floats": (c_size_t, [c_int, c_int, c_int, c_void_p]),
-    "vlsa_xchg_alloc": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p]),
-    "vlsa_xchg_open": (c_int, [c_void_p, c_void_p]),
-    "vlsa_xchg_close": (c_int, [c_void_p]),
-    "vlsa_xchg_free": (c_int, [c_void_p]),
-    "vlsa_xchg_put": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int64, c_void_p,
-                              c_void_p]),
-    "vlsa_xchg_wait": (c_int, [c_int, c_void_p, c_uint32, c_int64, c_void_p, c_void_p]),
-    "vlsa_xchg_collect": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_uint32, c_int64]
-                          + [c_void_p] * 9),
-}
+# ---- the C ABI, read from include/vlsa_hip.h: its #defines, structs and prototypes are the only statement of it ----
+# Not a C parser: it knows the few forms the header uses and refuses everything else (a guessed type is a shifted argument list).
+_SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "size_t": c_size_t, "float": c_float, "double": c_double,
+            "uint32_t": c_uint32, "unsigned int": c_uint32, "unsigned": c_uint32}
+
+
+def _constants(text: str) -> dict:
+    """{NAME: value} of every ``#define VLSA_<NAME> <integer>``: decimal, hex or a parenthesised negative"""
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+VLSA_(\w+)[ \t]+\(?[ \t]*(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*\)?[ \t]*$", text, flags=re.M)
+    return {name: int(value, 0) for name, value in found}
+
+
+def _structs(text: str):
+    """({name: ctypes.Structure} of every ``typedef struct name { ... } name;``, the text without them).  A member is a scalar of the
+    table or an unsigned char, a pointer to one of those or to void (c_void_p), or a pointer to an earlier struct (POINTER of it);
+    one declaration may hold several declarators."""
+    structs = {}
+    scalars = dict(_SCALARS, **{"unsigned char": c_ubyte})
+
+    def member(base, star):
+        if star:
+            return ctypes.POINTER(structs[base]) if base in structs else c_void_p if base in scalars or base == "void" else None
+        return scalars.get(base)
+
+    def one(m):
+        name, body, alias = m.groups()
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            head = re.fullmatch(r"(?:const )?((?:unsigned )?\w+)\b(.*)", decl)
+            items = [re.fullmatch(r" ?(\*?) ?(\w+) ?", d) for d in head.group(2).split(",")] if head else [None]
+            types = [it and member(head.group(1), it.group(1)) for it in items]
+            if not all(types):
+                raise VlsaNativeError(f"struct {name}: no ctypes type for the member declaration '{decl}'")
+            fields += [(it.group(2), t) for it, t in zip(items, types)]
+        if alias != name:
+            raise VlsaNativeError(f"struct {name} is typedef'd as {alias}")
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", one, text)
+    if re.search(r"\bstruct\b", text):
+        raise VlsaNativeError("a struct that is not written as 'typedef struct name { members } name;'")
+    return structs, text
+
+
+def _prototypes(text: str) -> dict:
+    """{name: (restype, [argtypes])} of every ``<ret> vlsa_name(<params>);`` of a text without comments, preprocessor lines and
+    structs.  Any pointer or array parameter is a c_void_p; a scalar outside the table, a struct by value, a function pointer,
+    ``...`` and any other ``vlsa_name(`` are errors."""
+    sigs = {}
+    for stmt in text.split(";"):
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(vlsa_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:
+            if re.search(r"\bvlsa_\w+\s*\(", stmt):
+                raise VlsaNativeError(f"not a prototype the binding can read: '{' '.join(stmt.split())}'")
+            continue
+        name = m.group(2)
+        ret, *params = (re.sub(r"\bconst\b", " ", t).split() for t in [m.group(1)] + m.group(3).split(","))
+        if "*" in "".join(ret):
+            res = c_char_p if "".join(ret) == "char*" else c_void_p
+        else:
+            res = _SCALARS.get(" ".join(ret))
+        args = []
+        for words in ([] if params == [["void"]] else params):
+            if "*" in "".join(words) or "[" in "".join(words):
+                args.append(c_void_p)
+            else:       # the type alone, or the type and a parameter name
+                args.append(_SCALARS.get(" ".join(words)) or _SCALARS.get(" ".join(words[:-1])))
+        if res is None or None in args or name in sigs:
+            raise VlsaNativeError(f"{name}: declared twice, or no ctypes type for its return value or a parameter: '{' '.join(stmt.split())}'")
+        sigs[name] = (res, args)
+    return sigs
+
+
+def read_header(text: str):
+    """(constants, structs, signatures) of a header text"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = _constants(text)
+    structs, text = _structs(re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M))
+    return constants, structs, _prototypes(text)
+
+
+try:
+    with open(_HEADER_PATH) as _f:
+        _CONSTANTS, STRUCTS, _SIGNATURES = read_header(_f.read())
+except OSError as exc:
+    raise VlsaNativeError(f"cannot read the C ABI header {_HEADER_PATH}: {exc}") from exc
+globals().update(_CONSTANTS)        # ABI_VERSION, DT_*, KERNEL_*, POOL_*, MAX_*, TT_PERSISTENT, ADAM_MAX_TENSORS, OK, EINVAL, EUNSUPPORTED, ELAUNCH
+P_STRIDE = 16                       # the header has no macro for the 16-float stride of the per-query statistics
+AdamTensor = STRUCTS["vlsa_adam_tensor"]
 
 _lib = None
 

@@ -25,21 +25,7 @@ from . import _native as nat
 from ._native import VlsaNativeError
 
 
-class _TTLayer(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("ln1_w", "ln1_b", "in_w", "in_b", "out_w", "out_b", "ln2_w", "ln2_b", "fc_w", "fc_b",
-                                               "proj_w", "proj_b")]
-
-
-class _TTModel(ctypes.Structure):
-    _fields_ = [("width", ctypes.c_int), ("heads", ctypes.c_int), ("layers", ctypes.c_int), ("out_dim", ctypes.c_int),
-                ("ctx_len", ctypes.c_int), ("layer", ctypes.POINTER(_TTLayer)), ("pos_emb", ctypes.c_void_p),
-                ("cls_emb", ctypes.c_void_p), ("lnf_w", ctypes.c_void_p), ("lnf_b", ctypes.c_void_p), ("text_proj", ctypes.c_void_p)]
-
-
-class _TTRows(ctypes.Structure):
-    _fields_ = [("n_seq", ctypes.c_int), ("M", ctypes.c_int), ("M_pad", ctypes.c_int), ("max_len", ctypes.c_int),
-                ("row_seq", ctypes.c_void_p), ("row_pos", ctypes.c_void_p), ("row_src", ctypes.c_void_p),
-                ("seq_row0", ctypes.c_void_p), ("cls_keep", ctypes.c_void_p), ("prefix_len", ctypes.c_int)]
+_TTLayer, _TTModel, _TTRows = (nat.STRUCTS[n] for n in ("vlsa_tt_layer", "vlsa_tt_model", "vlsa_tt_rows"))     # include/vlsa_hip.h
 
 
 # -- parameter holders with the reference's names (model/conch/transformer.py:191-247,290-322) ---------------------------
