@@ -614,6 +614,17 @@ typedef struct vlsa_tt_layer {
 
 /* The tower (HOST struct; `layer` is a HOST array of `layers` entries).  width % 128 == 0, width <= 768, 64 features per head
  * (CONCH: 768 / 12 heads / 12 layers, model/conch/model_configs/conch_ViT-B-16.json), out_dim % 64 == 0. */
+/* vlsa_tt_model.flags (0 = the CoCa tower above).  The two bits together are the CLIP text tower (OpenAI model/clip/model.py:166-168,
+ * 343-356 and HuggingFace CLIPTextTransformer with hidden_act quick_gelu): 512 / 8 heads / 12 layers / 77 positions for ViT-B.
+ *   VLSA_TT_ACT_QUICK_GELU   the MLP activation is x * sigmoid(1.702 x) instead of erf-GELU, in the forward, the input-gradient and the
+ *                            weight-gradient passes.
+ *   VLSA_TT_POOL_LAST_TOKEN  there is no CLS token: the pooled row of a prompt is its LAST compact row (seq_row0[s + 1] - 1), which is a
+ *                            token row like any other (row_src >= 0: the <eot> position; its gradient goes to d prompts_embedding),
+ *                            every row_src is >= 0, ctx_len counts positions only (77), cls_emb may be NULL and -- in `grads` -- is
+ *                            not written.  With cls_keep all ones the pooled row is causal like the rest.
+ * Any other bit is VLSA_EINVAL.  Flagged models always take the launch-per-stage forward (vlsa_tt_status_offset: -1). */
+#define VLSA_TT_ACT_QUICK_GELU 1
+#define VLSA_TT_POOL_LAST_TOKEN 2
 typedef struct vlsa_tt_model {
     int width, heads, layers, out_dim, ctx_len;  /* ctx_len = positions incl. the CLS slot (128) */
     const vlsa_tt_layer* layer;
@@ -621,6 +632,7 @@ typedef struct vlsa_tt_model {
     const float* cls_emb;    /* [width] */
     const float *lnf_w, *lnf_b; /* ln_final */
     const float* text_proj;  /* text_projection [width, out_dim] */
+    int flags;               /* VLSA_TT_ACT_* | VLSA_TT_POOL_*; 0: erf-GELU, pooled CLS row */
 } vlsa_tt_model;
 
 /* The compact rows of a batch of prompts (HOST struct of DEVICE int arrays, built once per prompt-length pattern).

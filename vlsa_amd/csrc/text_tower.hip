@@ -37,6 +37,11 @@
 //                         ln_final on the CLS rows, d prompts_embedding (the general route).
 // Backward is w.r.t. the prompt embeddings only: the tower is frozen in every shipped configuration
 // (vlsa_txt_encoder_frozen: True, cfg_vlsa_conch.yaml:69; runner/vlsa_handler.py:131).
+//
+// The CLIP text towers (vlsa_tt_model.flags; reference model/prompt_encoder.py:35-207 over model/clip/model.py:171-203) are the same
+// kernels: VLSA_TT_ACT_QUICK_GELU swaps the MLP activation (PRO_QUICK variants of the products with a GELU epilogue and of
+// k_tt_gelu_rows), VLSA_TT_POOL_LAST_TOKEN drops the CLS token -- a prompt's rows are its positions 0 .. <eot>, every one a token row,
+// the LAST one pooled (k_tt_lnf_fwd / k_tt_lnf_bwd find it by position; its gradient goes to d prompts_embedding like any row's).
 #include "vlsa_common.h"
 #include "launch.h"
 
@@ -51,6 +56,20 @@ constexpr int kHeadDim = 64;
 __device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad(float x) {
     return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
+}
+
+// QuickGELU of the CLIP towers (VLSA_TT_ACT_QUICK_GELU; OpenAI model/clip/model.py:166-168, HuggingFace hidden_act "quick_gelu"):
+// x * s with s = sigmoid(1.702 x).  The sigmoid goes through e = exp(-|z|) <= 1, so no z overflows, and the negative side is
+// e / (1 + e), not 1 - 1 / (1 + e'): at z = -17 (x = -10) that keeps the 4e-8 tail instead of rounding it to zero.  One v_exp_f32 and
+// one v_rcp_f32 (1 ulp each) per element, against erff's polynomial: the cheaper of the two epilogues.
+__device__ __forceinline__ float quick_sigmoid(float x) {
+    const float z = 1.702f * x, e = __expf(-fabsf(z)), r = __builtin_amdgcn_rcpf(1.f + e);
+    return z >= 0.f ? r : e * r;
+}
+__device__ __forceinline__ float quick_gelu(float x) { return x * quick_sigmoid(x); }
+__device__ __forceinline__ float quick_gelu_grad(float x) {
+    const float s = quick_sigmoid(x);
+    return fmaf(1.702f * x * s, 1.f - s, s);      // s + 1.702 x s (1 - s)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -112,7 +131,7 @@ __global__ __launch_bounds__(256) void k_tt_embed(float* __restrict__ x, float* 
 // A workgroup owns 16 MT rows x 32 columns; its NW waves split K (each wave streams KW = K / NW columns of both operands:
 // 1 KB per load instruction, each weight read exactly once from HBM per row group) and are reduced through LDS in a fixed
 // order (deterministic, no atomics).  Outputs: row-major Y and / or tiled Yt (the next product's A operand).
-enum { PRO_NONE = 0, PRO_LN = 1, PRO_LNBWD = 2 };
+enum { PRO_NONE = 0, PRO_LN = 1, PRO_LNBWD = 2, PRO_QUICK = 4 };      // PRO_QUICK: a flag or-ed to a prologue, see k_tt_gemm
 enum { EPI_BIAS = 1, EPI_RESID = 2, EPI_GELU = 4, EPI_GELU_BWD = 8 };
 constexpr int kSlabMax = 12;   // PRO_LN: (K / NW) / 16 groups of the A slab kept in registers (K <= 768 at NW = 4)
 
@@ -210,8 +229,13 @@ __device__ __forceinline__ void prefetch_next(const GemmArgs& p, int nthreads, f
     }
 }
 
-template <int MT, int NW, int PRO, int GT, int NTW = 2>
+// PROQ = the prologue (PRO_NONE / PRO_LN / PRO_LNBWD), or-ed with PRO_QUICK when the activation of EPI_GELU / EPI_GELU_BWD is QuickGELU
+// (VLSA_TT_ACT_QUICK_GELU): a compile-time variant, instantiated for the products that have such an epilogue only -- the erf kernels
+// keep their names and are, instruction for instruction, what they were without it
+template <int MT, int NW, int PROQ, int GT, int NTW = 2>
 __global__ __launch_bounds__(NW * 64) void k_tt_gemm(const GemmArgs p) {
+    constexpr int PRO = PROQ & 3;
+    constexpr bool QUICK = (PROQ & PRO_QUICK) != 0;
     extern __shared__ __attribute__((aligned(16))) float red[];
     constexpr int Q = MT * NTW * 4;        // accumulator registers per lane
     const int tid = threadIdx.x, lane = tid & 63;
@@ -663,9 +687,9 @@ __global__ __launch_bounds__(NW * 64) void k_tt_gemm(const GemmArgs p) {
         if (epi & EPI_BIAS) val += e_bias[i];
         if (epi & EPI_GELU) {
             if (p.Ypre) p.Ypre[(size_t)row * p.ldy + col] = val;
-            val = gelu(val);
+            val = QUICK ? quick_gelu(val) : gelu(val);
         }
-        if (epi & EPI_GELU_BWD) val *= gelu_grad(e_h[i]);
+        if (epi & EPI_GELU_BWD) val *= QUICK ? quick_gelu_grad(e_h[i]) : gelu_grad(e_h[i]);
         if (epi & EPI_RESID) val += e_res[i];
         if (p.Y && (p.M_store == 0 || row < p.M_store)) p.Y[(size_t)row * p.ldy + col] = val;
         if (p.Yt) p.Yt[tiled_index(row, col, N)] = val;
@@ -1150,11 +1174,13 @@ __global__ __launch_bounds__(256) void k_tt_lnf_fwd(const float* __restrict__ x,
         if (k < nslot) pooled[tiled_index(s, lane + 64 * k, d)] = fmaf((xv[k] - mean) * rstd, gv[k], bv[k]);
 }
 
-// dx[row] = ln_final backward of dpooled[s] on the CLS row of prompt s, zero on every other row.
+// dx[row] = ln_final backward of dpooled[s] on the pooled row of prompt s, zero on every other row.  The pooled row is the CLS row
+// (row_src < 0), or -- seq_row0 given: VLSA_TT_POOL_LAST_TOKEN -- the prompt's last row by position, seq_row0[s + 1] - 1 (a token row;
+// the shared-prefix rows belong to prompt 0 and lie in front of seq_row0[0], so they never match).
 __global__ __launch_bounds__(256) void k_tt_lnf_bwd(const float* __restrict__ dpooled, const float* __restrict__ x,
                                                    const int* __restrict__ row_seq, const int* __restrict__ row_src,
                                                    const float* __restrict__ gamma, float* __restrict__ dx, float* __restrict__ dxt,
-                                                   int d, int M, int M_pad) {
+                                                   int d, int M, int M_pad, const int* __restrict__ seq_row0) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M_pad) return;
     const int nslot = d >> 6;
@@ -1168,7 +1194,8 @@ __global__ __launch_bounds__(256) void k_tt_lnf_bwd(const float* __restrict__ dp
             xv[k] = x[(size_t)row * d + lane + 64 * k];
             gv[k] = gamma[lane + 64 * k];
         }
-    if (row >= M || rsrc >= 0) {
+    const bool pooled = row < M && (seq_row0 != nullptr ? seq_row0[s + 1] - 1 == row : rsrc < 0);
+    if (!pooled) {
         for (int k = 0; k < nslot; ++k) {
             dx[(size_t)row * d + lane + 64 * k] = 0.f;
             dxt[tiled_index(row, lane + 64 * k, d)] = 0.f;
@@ -1327,11 +1354,13 @@ __global__ __launch_bounds__(256) void k_tt_ln_rows(const float* __restrict__ x,
 
 // y = gelu(h) over the first `rows` rows of a row-major [.., C] matrix: the input of c_proj, which the forward only keeps as h_pre
 // (evaluating erf inside the weight-gradient product would repeat it 24 times per element: 37 us per block instead of 13 + 3)
+template <bool QUICK>
 __global__ __launch_bounds__(256) void k_tt_gelu_rows(const float* __restrict__ h, float* __restrict__ y, size_t n4) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n4) return;
     const f32x4 v = reinterpret_cast<const f32x4*>(h)[idx];
-    reinterpret_cast<f32x4*>(y)[idx] = f32x4{gelu(v[0]), gelu(v[1]), gelu(v[2]), gelu(v[3])};
+    if constexpr (QUICK) reinterpret_cast<f32x4*>(y)[idx] = f32x4{quick_gelu(v[0]), quick_gelu(v[1]), quick_gelu(v[2]), quick_gelu(v[3])};
+    else reinterpret_cast<f32x4*>(y)[idx] = f32x4{gelu(v[0]), gelu(v[1]), gelu(v[2]), gelu(v[3])};
 }
 
 // dgamma[c] = sum_n dy[n, c] xhat[row(n), c], dbeta[c] = sum_n dy[n, c] over n < count; row(n) = n, or the CLS row of prompt n
@@ -1364,7 +1393,7 @@ __global__ __launch_bounds__(256) void k_tt_ln_param_bwd(const float* __restrict
 }
 
 // d positional_embedding[p] = sum of dx0 over the compact rows at position p (block p < ctx_len; positions no row uses get zeros),
-// d cls_emb = sum over the CLS rows (block ctx_len).  model/prompt_encoder.py:283-292.  The matching rows are listed first (all
+// d cls_emb = sum over the CLS rows (block ctx_len; not launched for a tower without a CLS token).  model/prompt_encoder.py:283-292.  The matching rows are listed first (all
 // threads test rows in parallel, wave 0 compacts them in row order), then summed in that order.
 constexpr int kPosRowsMax = 1024;
 __global__ __launch_bounds__(256) void k_tt_pos_cls_bwd(const float* __restrict__ dx, const int* __restrict__ row_pos,
@@ -1779,7 +1808,7 @@ using namespace vlsa::tt;
 namespace {
 
 struct Shape {
-    int d, heads, layers, out_dim, M_pad, M, n_seq, ns_pad, L;
+    int d, heads, layers, out_dim, M_pad, M, n_seq, ns_pad, L, flags;
 };
 
 bool shape_of(const vlsa_tt_model* m, const vlsa_tt_rows* r, Shape& s) {
@@ -1791,7 +1820,10 @@ bool shape_of(const vlsa_tt_model* m, const vlsa_tt_rows* r, Shape& s) {
     // width: multiple of 128 (the K splits of every product are whole 16-column groups), <= 768 (fused-LayerNorm slab), 64 per head
     if (s.d < 128 || s.d > 768 || (s.d % 128) || s.heads * kHeadDim != s.d) return false;
     if (s.layers < 1 || s.out_dim < 64 || (s.out_dim % 64) || s.out_dim > 1024) return false;
-    if (!m->pos_emb || !m->cls_emb || !m->lnf_w || !m->lnf_b || !m->text_proj) return false;
+    s.flags = m->flags;
+    if (s.flags & ~(VLSA_TT_ACT_QUICK_GELU | VLSA_TT_POOL_LAST_TOKEN)) return false;
+    if (!m->pos_emb || !m->lnf_w || !m->lnf_b || !m->text_proj) return false;
+    if (!m->cls_emb && !(s.flags & VLSA_TT_POOL_LAST_TOKEN)) return false;     // the CLS row's embedding
     if (!r) return true;
     s.M = r->M;
     s.M_pad = r->M_pad;
@@ -1886,7 +1918,7 @@ static int tt_debug_bits_all() {
     return e ? (atoi(e) << 8) : 0;
 }
 #endif
-template <int MT, int NW, int PRO, int GT, int NTW = 2>
+template <int MT, int NW, int PRO, int GT, int NTW = 2, bool QUICK = false>
 int launch_gemm_g(GemmArgs a, int M_pad, hipStream_t st) {
 #ifdef VLSA_TT_DEBUG
     a.epi |= tt_debug_bits_all();     // experiments on EVERY product of the tower (results are then wrong: timing only)
@@ -1898,20 +1930,29 @@ int launch_gemm_g(GemmArgs a, int M_pad, hipStream_t st) {
     a.xcd_map = NT >= 8 ? 1 : 0;      // XCD-aware block -> tile map (whole rounds of 8 tiles; the rest linear)
     size_t lds = (size_t)NW * MT * NTW * 4 * 64 * sizeof(float);
     if (PRO != PRO_NONE && lds < (size_t)(1024 + 2 * a.K) * sizeof(float)) lds = (size_t)(1024 + 2 * a.K) * sizeof(float);
-    launch_lds<k_tt_gemm<MT, NW, PRO, GT, NTW>>(dim3(NT * a.MG), dim3(NW * 64), lds, st, a);
+    launch_lds<k_tt_gemm<MT, NW, PRO | (QUICK ? PRO_QUICK : 0), GT, NTW>>(dim3(NT * a.MG), dim3(NW * 64), lds, st, a);
     return launch_status();
 }
 // G1, G2: the group counts of the CONCH-size tower for this product (compile-time specialisations); anything else: runtime G
 // wide products (N a multiple of 48): 48-column workgroup tiles, see k_tt_gemm
-template <int MT, int NW, int PRO, int G1>
+template <int MT, int NW, int PRO, int G1, bool QUICK = false>
 int launch_gemm_wide(const GemmArgs& a, int M_pad, hipStream_t st) {
     const int G = a.K / NW / 16;
     if (a.N % 48 == 0) {
-        if (G == G1) return launch_gemm_g<MT, NW, PRO, G1, 3>(a, M_pad, st);
-        return launch_gemm_g<MT, NW, PRO, 0, 3>(a, M_pad, st);
+        if (G == G1) return launch_gemm_g<MT, NW, PRO, G1, 3, QUICK>(a, M_pad, st);
+        return launch_gemm_g<MT, NW, PRO, 0, 3, QUICK>(a, M_pad, st);
     }
-    if (G == G1) return launch_gemm_g<MT, NW, PRO, G1, 2>(a, M_pad, st);
-    return launch_gemm_g<MT, NW, PRO, 0, 2>(a, M_pad, st);
+    if (G == G1) return launch_gemm_g<MT, NW, PRO, G1, 2, QUICK>(a, M_pad, st);
+    return launch_gemm_g<MT, NW, PRO, 0, 2, QUICK>(a, M_pad, st);
+}
+// the products with a GELU epilogue: the same shape choice for either activation (`quick` selects the template variant)
+template <int MT, int NW, int PRO, int GT, int NTW>
+int launch_gemm_g_act(bool quick, const GemmArgs& a, int M_pad, hipStream_t st) {
+    return quick ? launch_gemm_g<MT, NW, PRO, GT, NTW, true>(a, M_pad, st) : launch_gemm_g<MT, NW, PRO, GT, NTW, false>(a, M_pad, st);
+}
+template <int MT, int NW, int PRO, int G1>
+int launch_gemm_wide_act(bool quick, const GemmArgs& a, int M_pad, hipStream_t st) {
+    return quick ? launch_gemm_wide<MT, NW, PRO, G1, true>(a, M_pad, st) : launch_gemm_wide<MT, NW, PRO, G1, false>(a, M_pad, st);
 }
 // 16-row workgroup tiles (the N = d products): 32-column tiles when the grid then still fits one round of the 256 CUs -- more
 // workgroups with a third less weight traffic each (the c_proj product moves the most bytes per workgroup: 18.7 -> ~10 us) --
@@ -2011,7 +2052,7 @@ bool persist_supported(const Shape& s, const vlsa_tt_rows* r, int flags) {
     // launch-per-stage path -- a stage's in-kernel hand-off (drain of the write-through stores + counter + poll + first round of sc1
     // loads, ~3.5 us) costs MORE than the ~3.2 us kernel boundary it replaces, and the 4-byte sc1 epilogue stores are 2x slower than
     // plain ones; the weight prefetch it buys (task bodies 5.8 vs 8.5 us for QKV) does not make up for it.  Kept, tested, off by default.
-    if (!(flags & VLSA_TT_PERSISTENT)) return false;
+    if (!(flags & VLSA_TT_PERSISTENT) || s.flags != 0) return false;      // (the persistent kernel knows the CoCa tower only)
     const int RT = (s.M + 15) / 16;       // 7 row tiles x 36 QKV column tiles = 252 workgroups: one round of the CUs
     return s.d == 768 && s.heads == 12 && s.layers <= kPMaxLayers && RT <= 7 && RT * 16 <= s.M_pad && r->max_len <= kPAttnMaxS
            && (s.n_seq + (s.L > 0 ? 1 : 0)) * s.heads <= 256;
@@ -2123,6 +2164,7 @@ extern "C" int vlsa_tt_forward(const vlsa_tt_model* m, const vlsa_tt_rows* r, co
     const float* wset = static_cast<const float*>(packed);
     auto region = [&](int layer) { return ws + (save_for_backward ? (size_t)layer : 0) * LF; };
 
+    const bool quick = (s.flags & VLSA_TT_ACT_QUICK_GELU) != 0;
     const bool keep_attn = save_for_backward == 2;          // a training tower: the attention output of every block stays
     const bool persist = !keep_attn && persist_supported(s, r, tt_flags);
     // tiled copies of a block's input / its middle: scratch, or -- kept for the backward pass -- behind the block's region
@@ -2226,10 +2268,10 @@ extern "C" int vlsa_tt_forward(const vlsa_tt_model* m, const vlsa_tt_rows* r, co
             // 32 x 64 workgroup tiles when they fit one round (K = 12 prompts: 5 x 48 = 240 workgroups, 160 instead of 192 rows of
             // f32-MFMA work -- this product is matrix-pipe-bound), else 48 x 48
             if ((4 * d) % 96 == 0 && ((s.M + 15) / 16) * (4 * d / 96) <= 256 && d / 4 / 16 == 12)
-                TT_TRY((launch_gemm_g<1, 4, PRO_LN, 12, 6>(a, Mp, st)));       // few rows: 16 x 96 tiles (7 x 32 = 224 workgroups)
+                TT_TRY((launch_gemm_g_act<1, 4, PRO_LN, 12, 6>(quick, a, Mp, st)));       // few rows: 16 x 96 tiles (7 x 32 = 224 workgroups)
             else if (Mp % 32 == 0 && (4 * d) % 64 == 0 && ((s.M + 31) / 32) * (4 * d / 64) <= 256 && d / 4 / 16 == 12)
-                TT_TRY((launch_gemm_g<2, 4, PRO_LN, 12, 4>(a, Mp, st)));
-            else TT_TRY((launch_gemm_wide<3, 4, PRO_LN, 12>(a, Mp, st)));
+                TT_TRY((launch_gemm_g_act<2, 4, PRO_LN, 12, 4>(quick, a, Mp, st)));
+            else TT_TRY((launch_gemm_wide_act<3, 4, PRO_LN, 12>(quick, a, Mp, st)));
         }
         {
             GemmArgs a = gemm_args(c.hact_t, pw.proj_w, d, 4 * d);
@@ -2285,6 +2327,7 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
     const size_t LF = layer_floats(s);
     const Scratch c = scratch_of(ws + (size_t)s.layers * LF, s);
     const float* bset = static_cast<const float*>(packed) + set_floats(s);
+    const bool quick = (s.flags & VLSA_TT_ACT_QUICK_GELU) != 0, pool_last = (s.flags & VLSA_TT_POOL_LAST_TOKEN) != 0;
 
     {   // d pooled = dout @ text_projection^T
         GemmArgs a = gemm_args(c.dout_t, packed_proj(bset, s), d, s.out_dim);
@@ -2300,10 +2343,10 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
         }
     }
     hipLaunchKernelGGL(k_tt_lnf_bwd, dim3((Mp + 3) / 4), dim3(256), 0, st, c.dpool, c.x_final, r->row_seq, r->row_src, m->lnf_w, c.dxa,
-                       c.dxa_t, d, s.M, Mp);
+                       c.dxa_t, d, s.M, Mp, pool_last ? r->seq_row0 : (const int*)nullptr);
     TT_LAUNCHED();
     if (gr) {
-        if (!gr->layer || !gr->pos_emb || !gr->cls_emb || !gr->lnf_w || !gr->lnf_b || !gr->text_proj || (d % 64) || d > 64 * kLnSlots)
+        if (!gr->layer || !gr->pos_emb || (!gr->cls_emb && !pool_last) || !gr->lnf_w || !gr->lnf_b || !gr->text_proj || (d % 64) || d > 64 * kLnSlots)
             return VLSA_EINVAL;
         if (s.M > kPosRowsMax) return VLSA_EUNSUPPORTED;
         // text_projection [d, out_dim]: pooled^T dout;  ln_final: gamma / beta from d pooled and the CLS rows of x_final
@@ -2358,12 +2401,12 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
             prefetch_for(a, true, pw.fc_w, d, 4 * d, 2);
             prefetch_region(a, layer_xmid_t(x_in, s), (size_t)Mp * d);      // ln_2 backward's x, two launches ahead
             if (top) {
-                TT_TRY((launch_gemm_g<1, 4, PRO_NONE, 12, 6>(a, Mp, st)));
+                TT_TRY((launch_gemm_g_act<1, 4, PRO_NONE, 12, 6>(quick, a, Mp, st)));
             } else {
                 a.X2 = layer_xin_t(ws + (size_t)(L + 1) * LF, s); a.R2 = c.dxb_t; a.ln_w = m->layer[L + 1].ln1_w;
                 a.Yt2 = c.dxa_t; a.Y2 = c.dxa; a.ld2 = d;
                 a.stats_in = layer_stats1(ws + (size_t)(L + 1) * LF, s);
-                TT_TRY((launch_gemm_g<1, 4, PRO_LNBWD, 12, 6>(a, Mp, st)));
+                TT_TRY((launch_gemm_g_act<1, 4, PRO_LNBWD, 12, 6>(quick, a, Mp, st)));
             }
         }
         {   // d ln_2 out = d h_pre @ W_fc   (tiled: the next product's prologue reads it)
@@ -2422,16 +2465,17 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
             a.Yt = c.dh_t; a.H = h_pre; a.ldh = 4 * d; a.epi = EPI_GELU_BWD;
             a.M_real = s.M;
             if ((4 * d) % 96 == 0 && ((s.M + 15) / 16) * (4 * d / 96) <= 256 && d / 4 / 16 == 12)
-                TT_TRY((launch_gemm_g<1, 4, PRO_NONE, 12, 6>(a, Mp, st)));
+                TT_TRY((launch_gemm_g_act<1, 4, PRO_NONE, 12, 6>(quick, a, Mp, st)));
             else if (Mp % 32 == 0 && (4 * d) % 64 == 0 && ((s.M + 31) / 32) * (4 * d / 64) <= 256 && d / 4 / 16 == 12)
-                TT_TRY((launch_gemm_g<2, 4, PRO_NONE, 12, 4>(a, Mp, st)));
-            else TT_TRY((launch_gemm_wide<3, 4, PRO_NONE, 12>(a, Mp, st)));
+                TT_TRY((launch_gemm_g_act<2, 4, PRO_NONE, 12, 4>(quick, a, Mp, st)));
+            else TT_TRY((launch_gemm_wide_act<3, 4, PRO_NONE, 12>(quick, a, Mp, st)));
         }
         const vlsa_tt_layer* g = gr ? &gr->layer[L] : nullptr;
         const float* attn_t = h_pre + (size_t)Mp * 4 * d;      // (kept by the forward with save == 2)
         if (g) {   // c_proj [d, 4d]: dx_out^T gelu(h_pre);  c_fc [4d, d]: d h_pre^T ln_2(x_mid)
             const size_t n4 = (size_t)s.M * d;               // s.M rows x 4 d columns in float4s; c.hact_t: forward scratch, free here
-            hipLaunchKernelGGL(k_tt_gelu_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, h_pre, c.hact_t, n4);
+            if (quick) hipLaunchKernelGGL(k_tt_gelu_rows<true>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, h_pre, c.hact_t, n4);
+            else hipLaunchKernelGGL(k_tt_gelu_rows<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, h_pre, c.hact_t, n4);
             TT_LAUNCHED();
             TT_TRY(launch_dw(DW_ROWS, c.dxa_t, c.hact_t, 4 * d, (float*)g->proj_w, (float*)g->proj_b, d, 4 * d, s.M, st));
             hipLaunchKernelGGL(k_tt_ln_rows, dim3((s.M + 3) / 4), dim3(256), 0, st, x_mid, w.ln2_w, w.ln2_b, c.lnout, c.lnstats, d, s.M);
@@ -2480,7 +2524,7 @@ int tt_backward(const vlsa_tt_model* m, const vlsa_tt_rows* r, const void* packe
         TT_LAUNCHED();
     }
     if (gr) {   // positional_embedding [ctx_len, d] and cls_emb [d] from the gradient of the embedded rows
-        hipLaunchKernelGGL(k_tt_pos_cls_bwd, dim3(m->ctx_len + 1), dim3(256), 0, st, c.dxa, r->row_pos, r->row_src, s.M, d, m->ctx_len,
+        hipLaunchKernelGGL(k_tt_pos_cls_bwd, dim3(m->ctx_len + (pool_last ? 0 : 1)), dim3(256), 0, st, c.dxa, r->row_pos, r->row_src, s.M, d, m->ctx_len,
                            (float*)gr->pos_emb, (float*)gr->cls_emb);
         TT_LAUNCHED();
     }

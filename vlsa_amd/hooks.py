@@ -8,13 +8,23 @@ calls a *hook*.
     set_tokenizer_factory(fn)    fn(root=..., name=..., api=...) -> tokenizer with the reference wrapper's contract:
                                  ``tok(text | [texts], return_raw_tokens, return_num_tokens)`` and the attributes
                                  ``bos_token_id / eos_token_id / pad_token_id``
-    set_vl_model_loader(fn)      fn(text_encoder_cfg=..., root=..., api=...) -> object with ``.text`` (a CoCa text tower: the
-                                 attributes CONCHPromptEncoder adopts, model/prompt_encoder.py:213-243) and ``.logit_scale``
+    set_vl_model_loader(fn)      fn(text_encoder_cfg=..., root=..., api=...) -> object with ``.logit_scale`` and what the API's prompt
+                                 encoder adopts (model/prompt_encoder.py): CONCH ``.text`` (a CoCa text tower, 213-243); CLIP
+                                 ``.transformer / .positional_embedding / .ln_final / .text_projection / .token_embedding`` (39-47);
+                                 HF ``.text_model`` and ``.text_projection`` of a ``transformers`` ``CLIPModel`` (106-127)
 
 Defaults (no hook installed): the host application's own loaders when they are importable -- running inside the reference's
 tree, ``model.utils_vl.Tokenizer`` and ``model.conch.create_model_from_pretrained`` (the calls model/utils_vl.py:27-41,116-123
 make); otherwise the ``conch`` pip package of mahmoodlab/CONCH.  Neither being importable raises with instructions; nothing
 here falls back to a CPU computation of the hot path.
+
+The CLIP and HF defaults read LOCAL files only -- nothing here downloads (the reference's ``clip._download`` is not reached):
+
+    CLIP   ``<root>/openai_clip/<name with '/' as '-'>.pt`` (where model/utils_vl.py:96-100 stores 'ViT-B/16' as ViT-B-16.pt): a
+           TorchScript archive or a pickled state dict in OpenAI's layout; only its text side is built (``load_openai_clip_text``)
+    HF     the directory ``<root>/<name>`` ('openai/clip-vit-base-patch16', 'vinid/plip') through
+           ``transformers.CLIPModel.from_pretrained(..., local_files_only=True)``
+A missing file raises ``FileNotFoundError`` with the path that was expected.
 """
 from __future__ import annotations
 
@@ -54,9 +64,16 @@ def make_tokenizer(root, name, api):
 def load_vl_model(text_encoder_cfg, root, api):
     if _vl_model_loader is not None:
         return _vl_model_loader(text_encoder_cfg=text_encoder_cfg, root=root, api=api)
+    if api == "CLIP":
+        return load_openai_clip_text(osp.join(root, "openai_clip", text_encoder_cfg["name"].replace("/", "-") + ".pt"))
+    if api == "HF":
+        path = osp.join(root, text_encoder_cfg["name"])
+        if not osp.isfile(osp.join(path, "config.json")):
+            raise FileNotFoundError(f"vlsa_api='HF': no HuggingFace CLIP model directory (config.json + weights) at {path}")
+        from transformers import CLIPModel
+        return CLIPModel.from_pretrained(path, local_files_only=True)
     if api != "CONCH":
-        raise NotImplementedError(f"vlsa_api={api!r}: the HIP text tower implements the CONCH (CoCa) text transformer only "
-                                  "(cfg_vlsa_conch.yaml:39); install a loader with vlsa_amd.hooks.set_vl_model_loader for other towers")
+        raise ValueError(f"Got an invalid api ({api}).")
     ckpt = osp.join(root, text_encoder_cfg["name"], "pytorch_model.bin")
     create = None
     try:
@@ -68,3 +85,31 @@ def load_vl_model(text_encoder_cfg, root, api):
             raise RuntimeError("no CONCH model loader: call vlsa_amd.hooks.set_vl_model_loader(fn), or make the reference's "
                                "`model.conch` / the `conch` package importable") from exc
     return create("conch_ViT-B-16", checkpoint_path=ckpt, return_transform=False)
+
+
+def load_openai_clip_text(path):
+    """The text side of an OpenAI CLIP checkpoint on the CPU: ``path`` is the ``.pt`` file OpenAI distributes (a TorchScript archive)
+    or a pickled state dict in the same layout (model/clip/model.py:399-436 reads the same keys).  Sizes come from the tensors:
+    width = ``ln_final.weight``, heads = width / 64, blocks counted from the keys.  fp16 tensors are widened to fp32 (exact)."""
+    import torch
+    import torch.nn as nn
+    from .prompt_encoder import CLIPPromptEncoder
+    if not osp.isfile(path):
+        raise FileNotFoundError(f"vlsa_api='CLIP': no OpenAI CLIP checkpoint at {path} (this package reads local files only; "
+                                "put the .pt file there, or install a loader with vlsa_amd.hooks.set_vl_model_loader)")
+    try:
+        sd = torch.jit.load(path, map_location="cpu").state_dict()
+    except RuntimeError:
+        sd = torch.load(path, map_location="cpu")
+    if hasattr(sd, "state_dict"):          # a pickled module
+        sd = sd.state_dict()
+    sd = {k: v.float() for k, v in sd.items()
+          if k.split(".")[0] in ("transformer", "positional_embedding", "ln_final", "text_projection", "token_embedding", "logit_scale")}
+    width = sd["ln_final.weight"].shape[0]
+    layers = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks.")})
+    tower = CLIPPromptEncoder(width=width, heads=width // 64, layers=layers, context_length=sd["positional_embedding"].shape[0],
+                              vocab_size=sd["token_embedding.weight"].shape[0], output_dim=sd["text_projection"].shape[1])
+    logit_scale = sd.pop("logit_scale")
+    tower.load_state_dict(sd)
+    tower.logit_scale = nn.Parameter(logit_scale.reshape(()))      # what VLSA adopts next to the tower (model/vlsa.py:105)
+    return tower

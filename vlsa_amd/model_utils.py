@@ -68,13 +68,12 @@ def Deep_VLSA(**kws):
 
 
 def get_prompt_encoder(vl_model, api):
-    """model/prompt_encoder.py:22-33.  CONCH: the HIP text tower adopting ``vl_model.text``.  The OpenAI-CLIP / HuggingFace
-    towers are alternative backbones no shipped config uses (cfg_vlsa_conch.yaml:39) and are not built."""
-    if api == "CONCH":
-        from .prompt_encoder import CONCHPromptEncoder
-        return CONCHPromptEncoder(vl_model)
-    if api in ("CLIP", "HF"):
-        raise NotImplementedError(f"vlsa_api={api!r}: only the CONCH text tower has a HIP implementation")
+    """model/prompt_encoder.py:22-33.  CONCH: the HIP text tower adopting ``vl_model.text``; CLIP / HF: the same tower machinery over
+    the text side of an OpenAI CLIP model / a ``transformers`` ``CLIPModel`` (QuickGELU, <eot> pooling)."""
+    from . import prompt_encoder as pe
+    classes = {"CONCH": pe.CONCHPromptEncoder, "CLIP": pe.CLIPPromptEncoder, "HF": pe.HFCLIPPromptEncoder}
+    if api in classes:
+        return classes[api](vl_model)
     raise ValueError(f"Got an invalid api ({api}).")
 
 
@@ -157,6 +156,8 @@ def patch_reference(resident_bags: bool = False, defer_training_calls: bool = Tr
       model from the handler's unmodified ``arch_cfg``;
     * ``model.deepmil.{VLFAN, FeatMIL, DeepMIL, logit_pooling}`` -> this package's: the name lookup of
       model/utils_vl.py:129-138 and ``utils/model_inference.py`` see the same classes.
+    * ``model.prompt_encoder.{CLIPPromptEncoder, HFCLIPPromptEncoder}`` -> this package's, when that module is importable: the
+      reference's own ``get_prompt_encoder(vl_model, 'CLIP' | 'HF')`` (model/prompt_encoder.py:22-33) then builds the HIP towers.
     * ``model.utils.DeepMIL``, ``model.utils.DSMIL`` and ``model.deepmil.DSMIL`` -> this package's: ``load_model('DeepMIL', dims,
       network='ABMIL' | 'MaxMIL' | 'MeanMIL' | 'DSMIL')`` (model/utils.py:67-91), i.e. ``SAHandler.func_load_model``, builds the
       HIP baselines.
@@ -188,6 +189,14 @@ def patch_reference(resident_bags: bool = False, defer_training_calls: bool = Tr
     saved["sa_baselines"] = [(mod, attr, getattr(mod, attr, _ABSENT)) for mod, attr in
                              ((ref_utils, "DeepMIL"), (ref_utils, "DSMIL"), (ref_mil, "DSMIL"))]
     ref_utils.DeepMIL, ref_utils.DSMIL, ref_mil.DSMIL = fast.DeepMIL, fast.DSMIL, fast.DSMIL
+    try:                                   # (absent where only a part of the reference's tree is importable)
+        import model.prompt_encoder as ref_pe
+    except ImportError:
+        ref_pe = None
+    if ref_pe is not None:
+        from . import prompt_encoder as pe
+        saved["prompt_encoders"] = [(ref_pe, attr, getattr(ref_pe, attr, _ABSENT)) for attr in ("CLIPPromptEncoder", "HFCLIPPromptEncoder")]
+        ref_pe.CLIPPromptEncoder, ref_pe.HFCLIPPromptEncoder = pe.CLIPPromptEncoder, pe.HFCLIPPromptEncoder
     if resident_bags:
         import sys
         import dataset.utils as ref_ds
@@ -277,7 +286,7 @@ def unpatch_reference(saved) -> None:
     ref_utils.VLSA, ref_vlsa.VLSA = saved["VLSA_utils"], saved["VLSA_vlsa"]
     ref_mil.VLFAN, ref_mil.FeatMIL, ref_mil.DeepMIL = saved["VLFAN"], saved["FeatMIL"], saved["DeepMIL"]
     ref_mil.logit_pooling = ref_vlsa.logit_pooling = saved["logit_pooling"]
-    for mod, attr, original in saved.get("sa_baselines", ()):
+    for mod, attr, original in list(saved.get("sa_baselines", ())) + list(saved.get("prompt_encoders", ())):
         if original is _ABSENT:
             if hasattr(mod, attr):
                 delattr(mod, attr)
