@@ -125,6 +125,14 @@ def main():
         bags, tb, ev = batches[step % 2]
         loss = stepper.step(bags, tb, ev)
         print(f"[train]  step {step}: loss {loss.item():.4f}")
+    # ... and the reference's own sampler, DataLoader(shuffle=True): no batch repeats, so the patients stay in ONE resident BagSet and every
+    # step's bags and labels are picked on the device (set_epoch / step_next): one graph for the full batch, one for the epoch's tail
+    source, bs = arena.bag_set(pids), min(16, len(pids))
+    for epoch in range(2):
+        stepper.set_epoch(source, t_bin, event, torch.randperm(len(pids), generator=g), batch_size=bs)
+        losses = [stepper.step_next().item() for _ in range(-(-len(pids) // bs))]
+        print(f"[train]  reshuffled epoch {epoch}: {len(losses)} steps of <= {bs} patients, mean loss {sum(losses) / len(losses):.4f}")
+    stepper.check_epoch()                                                  # the last epoch's gather status (set_epoch reads the earlier ones)
     print(f"[train]  {stepper.describe()}")
 
     # 4. interpretation -----------------------------------------------------------------------------------------------

@@ -599,6 +599,24 @@ typedef struct vlsa_adam_tensor {
 int vlsa_adam_step(const vlsa_adam_tensor* tensors, int n_tensors, const float* hyper, int* state, double beta1, double beta2, double eps,
                    void* stream);
 
+/*
+ * The sampler of the training step on the device (the reference draws its 32-bag batches with DataLoader(shuffle=True),
+ * runner/base_handler.py:241): ONE launch of one workgroup copies the next B picks of an epoch's order out of a resident set into
+ * slots at fixed addresses, so a captured step that reads the slots serves every batch.  No host data is read: capturable.
+ *   src_desc [M] vlsa_bag_desc rows, t_all [M] int64, e_all [M] fp32: the resident set and its labels;
+ *   order [L] int64: the epoch's order (indices into the set); cursor [1] int64: picks consumed so far;
+ *   slot_desc [B] vlsa_bag_desc rows, t_slot [B], e_slot [B]: the slots;  1 <= B <= vlsa_batch_max_bags().
+ * With c = *cursor: slot j <- set entry order[c + j] (descriptor row, t, e) for j < B, then *cursor = c + B.
+ * Every pick is checked BEFORE anything is written (a wrong descriptor row is a device fault in the streaming kernels): with c < 0 or
+ * c + B > L (VLSA_GATHER_BAD_CURSOR), or a pick outside [0, M) (VLSA_GATHER_BAD_INDEX), the launch writes that code into status [1]
+ * (int32) and nothing else -- slots and cursor keep the previous valid batch.  A good launch leaves status alone: the caller zeroes
+ * it and reads it when it likes (once per epoch).
+ */
+#define VLSA_GATHER_BAD_CURSOR 1
+#define VLSA_GATHER_BAD_INDEX 2
+int vlsa_batch_gather(const void* src_desc, const int64_t* t_all, const float* e_all, int64_t M, const int64_t* order, int64_t L,
+                      int B, int64_t* cursor, void* slot_desc, int64_t* t_slot, float* e_slot, int* status, void* stream);
+
 /* ---- text side: the frozen CoCa text tower on the prompts' compact rows -------------------------- */
 
 /* One pre-LN transformer block (model/conch/transformer.py:191-247): DEVICE pointers to fp32 tensors in the layouts

@@ -799,6 +799,83 @@ class BagSet(list):
         return self._desc
 
 
+class BagSlots(BagSet):
+    """``batch`` slots over a resident ``source`` set, for a sampler that reshuffles: a ``BagSet`` whose descriptor table ``desc()`` and
+    label tensors ``t`` / ``e`` are ONE device allocation each for the life of the object, refilled in the stream by ``gather``
+    (``vlsa_batch_gather``: the next ``batch`` picks of a device-side order).  Launches that read the slots by address -- and a hipGraph
+    that captured them -- then serve every batch drawn from the source (``TrainStep.step_next``).
+
+    ``groups()`` is ONE value for the life of the object: a captured launch has it baked in, and it decides how a bag's rows are split into
+    partial sums.  Default: ``vlsa_batch_groups`` over a representative batch (every ``M // batch``-th of the source's sorted sizes);
+    ``groups=`` overrides it (a power of two <= batch).
+
+    The host's view (the list's tensors, ``rows``, ``sizes``) follows the slots only where ``follow(indices)`` is called -- the eager
+    steps, which read sizes on the host; replayed launches read the device table alone.  ``t_all`` / ``e_all``: the source's labels on
+    its device ([M] int64 / float32; None: label slots of zeros).  The slots start out holding source bags ``0 .. batch - 1``."""
+
+    def __init__(self, source: BagSet, batch: int, groups: Optional[int] = None, t_all: Optional[torch.Tensor] = None,
+                 e_all: Optional[torch.Tensor] = None):
+        if not isinstance(source, BagSet):
+            raise ValueError(f"BagSlots takes a BagSet as its source (checked, resident bags), got {type(source).__name__}")
+        batch, M = int(batch), len(source)
+        max_bags = int(nat.load().vlsa_batch_max_bags())
+        if batch > max_bags:
+            raise ValueError(f"BagSlots: batch {batch} is above the {max_bags} bags a batched launch takes")
+        if not (1 <= batch <= M):
+            raise ValueError(f"BagSlots: batch {batch} outside [1, {M}] (the source holds {M} bags)")
+        dev = source[0].device
+        for name, lab, dtype in (("t_all", t_all, torch.int64), ("e_all", e_all, torch.float32)):
+            if lab is None:
+                continue
+            if lab.dim() != 1 or lab.shape[0] != M:
+                raise ValueError(f"BagSlots: {name} has shape {tuple(lab.shape)}, the source holds {M} bags")
+            if lab.device != dev:
+                raise ValueError(f"BagSlots: {name} is on {lab.device}, the source's bags are on {dev}")
+            if lab.dtype != dtype or not lab.is_contiguous():
+                raise ValueError(f"BagSlots: {name} must be a contiguous {dtype} tensor")
+        if groups is None:
+            rep = sorted(source.sizes)[::max(1, M // batch)][:batch]
+            groups = choose_groups(rep, 0)
+        groups = int(groups)
+        if groups < 1 or groups > batch or groups & (groups - 1):
+            raise ValueError(f"BagSlots: groups = {groups} is no power of two in [1, {batch}]")
+        first = list(range(batch))
+        super().__init__([source[i] for i in first], source.D, _rows=source.rows[first])
+        self.dt = source.dt
+        self.source, self.batch, self._fixed_groups = source, batch, groups
+        self.t_all = t_all if t_all is not None else torch.zeros(M, dtype=torch.int64, device=dev)
+        self.e_all = e_all if e_all is not None else torch.zeros(M, dtype=torch.float32, device=dev)
+        self._desc = _stage_table(self.rows, dev, "a BagSlots table (built outside a capture)")     # its own allocation, for good
+        self.t, self.e = self.t_all[:batch].clone(), self.e_all[:batch].clone()
+
+    def groups(self, reserved_cus: int = 0) -> int:
+        return self._fixed_groups
+
+    def follow(self, indices) -> None:
+        """the host's view of the slots after a ``gather`` of these source indices (the eager path reads sizes on the host)"""
+        idx = [int(i) for i in indices]
+        if len(idx) != self.batch:
+            raise ValueError(f"BagSlots.follow: {len(idx)} indices for {self.batch} slots")
+        src = self.source
+        self[:] = [src[i] for i in idx]
+        self.rows = src.rows[idx]
+        self.sizes = tuple(int(n) for n in self.rows[:, 1])
+        # everything a BagSet keeps that was derived from the previous rows: sub-sets, and the chunk plans of the table-driven routes
+        # (``_ChunkPlan.of``: row offsets, tile / part tables, buffer sizes -- a stale one against the new table is an out-of-bounds write)
+        self._chunks.clear()
+        self._groups.clear()
+        self.__dict__.pop("_plans", None)
+
+    def gather(self, order: torch.Tensor, L: int, cursor: torch.Tensor, status: torch.Tensor) -> None:
+        """ONE launch on the current stream: slots <- source entries ``order[cursor : cursor + batch]``, cursor += batch; a cursor or an
+        index out of range leaves everything as it was and a nonzero code in ``status`` (int32 [1]).  order: int64 device buffer holding
+        at least L entries; cursor: int64 [1].  The host's view does not move: ``follow``."""
+        src = self.source
+        nat.check(nat.load().vlsa_batch_gather(_p(src.desc()), _p(self.t_all), _p(self.e_all), len(src), _p(order), int(L), self.batch,
+                                               _p(cursor), _p(self._desc), _p(self.t), _p(self.e), _p(status), _stream()),
+                  "vlsa_batch_gather")
+
+
 _BATCH_BAGS = "the batched path takes bags with D == 512, one dtype (bf16 or fp32) and one device per batch"
 
 
