@@ -269,8 +269,9 @@ def test_provider_key_sees_reassigned_parameters_without_walking_per_call(hooks_
     re-assigned learner parameter -- same ``_version`` as the old one -- must change the key; an unrelated module built elsewhere must not."""
     model, _ = _build()
     walks = []
-    orig = type(model)._walk_module
-    type(model)._walk_module = staticmethod(lambda m: (walks.append(type(m).__name__), orig(m))[1])
+    from vlsa_amd import model_state
+    orig = model_state._walk_module
+    model_state._walk_module = lambda m: (walks.append(type(m).__name__), orig(m))[1]
     try:
         k0 = model._provider_key()
         n0 = len(walks)
@@ -288,4 +289,4 @@ def test_provider_key_sees_reassigned_parameters_without_walking_per_call(hooks_
         model.prompt_encoder.eval() if model.prompt_encoder.training else model.prompt_encoder.train()
         assert model._provider_key() != k1                                             # train / eval flag
     finally:
-        type(model)._walk_module = staticmethod(orig)
+        model_state._walk_module = orig

@@ -48,8 +48,9 @@ def test_text_features_are_computed_once_per_parameter_version():
         for _ in range(5):
             b = model.forward_text_only()
         assert tower.calls == 1 and b is a
-        assert model._tower_lists is not None and model._tower_lists[0] is tower
-        n_tensors = len(model._tower_lists[2])
+        watch = model._get_watches()["prompt_encoder"]
+        assert watch.module is tower
+        n_tensors = len(watch.lists()[1])
         assert n_tensors == sum(1 for _ in tower.parameters()) + sum(1 for _ in tower.buffers())
         # in-place edit of a tower weight, of a learner parameter: each is a new version
         tower.blocks[1][0].weight.mul_(1.5)
@@ -103,7 +104,8 @@ def test_a_parameter_object_swapped_inside_the_tower_is_seen_at_the_next_miss():
         learner.context_embeds.add_(0.0)           # any tracked change -> a miss -> the tower is walked again
         b = model.forward_text_only()
         assert tower.calls == 2
-        assert any(t is tower.proj.weight for t in model._tower_lists[2]) and not any(t is old for t in model._tower_lists[2])
+        walked = model._get_watches()["prompt_encoder"].lists()[1]
+        assert any(t is tower.proj.weight for t in walked) and not any(t is old for t in walked)
         tower.proj.weight.mul_(0.5)                # ... and the new object is tracked from then on
         c = model.forward_text_only()
         assert tower.calls == 3 and not torch.equal(b, c)
@@ -135,10 +137,11 @@ def test_deepcopy_and_pickle_drop_the_native_caches():
     model._plans["x"] = ctypes.pointer(ctypes.c_int(3))            # what a used model holds: native handles
     model._train_plans["y"] = ctypes.pointer(ctypes.c_int(4))
     twin = copy.deepcopy(model)
-    assert twin._plans == {} and twin._train_plans == {} and twin._text_cache is None and twin._tower_lists is None
+    assert twin._plans == {} and twin._train_plans == {} and twin._text_cache is None
+    assert "_watches" not in twin.__dict__ and twin._get_watches()["prompt_encoder"].lists() == ([], [])
     with torch.no_grad():
         assert torch.equal(twin.forward_text_only(), a)            # same parameters, caches rebuilt on use
-    assert twin.prompt_encoder is not tower and twin._tower_lists[0] is twin.prompt_encoder
+    assert twin.prompt_encoder is not tower and twin._get_watches()["prompt_encoder"].module is twin.prompt_encoder
     buf = io.BytesIO()
     torch.save(model, buf)
     buf.seek(0)

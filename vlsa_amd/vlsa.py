@@ -14,7 +14,6 @@ exact: it is recomputed whenever an optimizer step (or any in-place update) touc
 from __future__ import annotations
 
 import math
-import operator
 import os
 import random
 from typing import Callable, Optional
@@ -26,40 +25,17 @@ import torch.nn.functional as F
 from . import deepmil as mil_encoders
 from . import functional as VF
 from .deepmil import FeatMIL, VLFAN, logit_pooling
+from .model_state import _HOOKS_INSTALLED, ModuleWatch, _install_structure_hooks     # noqa: F401  (re-exported: the tests read them here)
 
 
-_GET_TRAINING, _GET_VERSION = operator.attrgetter("training"), operator.attrgetter("_version")    # C-level loops in _provider_key
 _PLAIN = frozenset((str, int, float, bool, type(None)))
 
-# Structure epoch: bumped whenever ANY nn.Module in the process registers a parameter, buffer or submodule (torch's global registration
-# hooks; `module.x = nn.Parameter(...)` goes through them).  Module / tensor lists kept for the cache keys below are valid for the epoch
-# they were walked in -- a re-assigned parameter of the prompt learner is seen at the next key, without walking the learner per call.
-# SIDE EFFECT (documented in INTEGRATION.md 5): the hooks are process-global -- one Python callback per registration in ANY model of the
-# process -- and are installed when the first ``VLSA`` is assembled, not at import.  Removals (``del m.weight``, writes to
-# ``m._parameters[...]``) are not registrations: the keys additionally re-walk on every cache miss, ``_apply`` and ``load_state_dict``.
-_STRUCT_EPOCH = [0, 0]          # [registrations seen, walks that found a changed structure]
-
-
-def _bump_structure_epoch(*_args, **_kwargs):
-    _STRUCT_EPOCH[0] += 1
-    return None
-
-
-_HOOKS_INSTALLED = [False]
-
-
-def _install_structure_hooks():
-    """Idempotent.  Called from ``VLSA._assemble`` AND lazily from ``_provider_key`` / ``_encoder_lists``: a model unpickled in a fresh
-    process (``torch.save(model)`` / ``copy``: ``TransientCaches.__getstate__``) never runs ``_assemble``, and without the hooks a
-    re-assigned provider parameter would keep the stale key."""
-    if _HOOKS_INSTALLED[0]:
-        return
-    _HOOKS_INSTALLED[0] = True
-    _STRUCT_EPOCH[0] += 1          # lists walked before the hooks existed are not trusted
-    from torch.nn.modules import module as _m
-    _m.register_module_parameter_registration_hook(_bump_structure_epoch)
-    _m.register_module_buffer_registration_hook(_bump_structure_epoch)
-    _m.register_module_module_registration_hook(_bump_structure_epoch)
+# Invalidation levels of ``VLSA._invalidate`` -- the ONE statement of what each event clears:
+#                                              _la   text cache   watches   _hot   _plans   _train_plans   _prepared_text / _query
+#   _FORWARD  a differentiable forward          x
+#   _WEIGHTS  load_state_dict                   x        x           x        x
+#   _STORAGE  _apply (.to / .cuda / .float)     x        x           x        x       x          x                  x
+_FORWARD, _WEIGHTS, _STORAGE = 0, 1, 2
 
 
 def _env_flag(name: str) -> bool:
@@ -96,6 +72,31 @@ def build_mil_encoder(image_encoder_cfg: dict) -> nn.Module:
     return cls(**image_encoder_cfg)
 
 
+def _device_bags_512(bags) -> bool:
+    """a non-empty list of device bags [..., N > 0, 512] of one dtype: what the batched HIP routes take"""
+    return len(bags) > 0 and all(x.is_cuda and x.dtype == bags[0].dtype and x.shape[-1] == 512 and x.shape[-2] > 0 for x in bags)
+
+
+def _encoder_extras(model):
+    """the encoder watch's extras (a function of the model: no reference back to it): logit scale, plain-attribute co-attention scale"""
+    cs = getattr(model._modules["mil_encoder"], "coattn_logit_scale", None)
+    return [model._parameters["logit_scale"]] + ([cs] if isinstance(cs, torch.Tensor) else [])
+
+
+class _ById:
+    """stands for an object in a cache key: equal to another ``_ById`` of the SAME object only, and keeps the object alive"""
+    __slots__ = ("obj",)
+
+    def __init__(self, obj):
+        self.obj = obj
+
+    def __eq__(self, other):
+        return other.__class__ is _ById and other.obj is self.obj
+
+    def __hash__(self):
+        return id(self.obj)
+
+
 class _DeferredCoopFeatures:
     """Text features of a CoOp-pretrained, frozen prompt learner (model/vlsa.py:129-137) -- a tower pass that waits for the device.
     A plain object (picklable; deep copies of the model stay bound to their own encoder), see prompt_adapter._DeferredTowerPass."""
@@ -115,9 +116,9 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
     calls from ``VLSAHandler.func_load_model`` (runner/vlsa_handler.py:112-120).  ``VLSA.from_modules(image_encoder_cfg, ...)``
     assembles the same model from ready-made parts (text features / provider / prompt learner + encoder objects)."""
 
-    _transient = {"_hot": dict, "_plans": dict, "_train_plans": dict, "_provider_lists": dict, "_text_cache": lambda: None,
+    _transient = {"_hot": dict, "_plans": dict, "_train_plans": dict, "_watches": None, "_text_cache": lambda: None,
                   "_text_cache_key": lambda: None, "_prepared_text": lambda: None, "_prepared_query": lambda: None,
-                  "_head_tickets": lambda: VF.HeadTickets(), "_la": lambda: None, "_la_lists": lambda: None,
+                  "_head_tickets": lambda: VF.HeadTickets(), "_la": lambda: None,
                   "_pending_calls": lambda: None, "_materialising": lambda: False, "_side_streams": None}
 
     #: bags per look-ahead window: an evaluation loop that calls ``net(X)`` once per bag of a ``vlsa_amd.ingest.ResidentBags`` dataset
@@ -186,7 +187,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
     def _assemble(self, image_encoder_cfg, text_provider=None, pretrained_text_features=None, query_network=None,
                   prompt_learner=None, prompt_encoder=None, logit_scale=math.log(1 / 0.07), cache_text_features=True, kwargs=None,
                   frozen_coop_features=False):
-        _install_structure_hooks()      # process-global registration hooks (see _STRUCT_EPOCH): only once a VLSA model exists
+        _install_structure_hooks()      # process-global registration hooks (vlsa_amd/model_state.py): only once a VLSA model exists
         self.kwargs = kwargs or {}
         self.image_encoder_cfg = dict(image_encoder_cfg)
         self.mil_encoder = build_mil_encoder(self.image_encoder_cfg)
@@ -219,8 +220,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         else:
             self.text_provider = text_provider
         self.cache_text_features = cache_text_features
-        self._text_cache = None
-        self._text_cache_key = None
+        self._drop_text_cache()
         if isinstance(logit_scale, nn.Parameter):
             self.logit_scale = logit_scale             # the VL model's own parameter (model/vlsa.py:105)
         else:
@@ -228,8 +228,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         self._plans = {}
         self._hot = {}                 # (D, dtype, device) -> (eval state, pre-built per-bag call, row stride): see _fused_vlfan
         self._train_plans = {}
-        self._provider_lists = {}                              # provider module -> (module, submodules, tensors, structure epoch)
-        self._la = self._la_lists = None                      # look-ahead window + kept module / tensor lists (see _lookahead)
+        self._la = None                                        # look-ahead window (see _lookahead)
         self._pending_calls, self._materialising = None, False  # deferred training calls (vlsa_amd/deferred.py)
         self._head_tickets = VF.HeadTickets()
         self._prepared_text, self._prepared_gen = None, 0     # see _fused_vlfan: what the plans' prepared T^ / queries were computed from
@@ -267,84 +266,82 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         cfg.update(tokenizer=self.text_tokenizer, num_prompts=cfg["num_ranks"], pretrained_prompt_features=features)
         return load_prompt_adapter(self.prompt_encoder, cfg)
 
-    # -- text side -----------------------------------------------------------------------------------------
-    def _provider_modules(self):
-        mods = (getattr(self, n, None) for n in ("prompt_learner", "prompt_encoder", "prompt_adapter"))
-        return [m for m in mods if isinstance(m, nn.Module)]
+    # -- model state: one kept walk per provider module and one for the MIL encoder (vlsa_amd/model_state.py states the rules), the
+    #    keys of the text cache, of the look-ahead / hot call and of the deferred training calls over them, and what clears what ------
+    _PROVIDER_NAMES = ("prompt_learner", "prompt_encoder", "prompt_adapter")
 
-    def _provider_key(self):
-        """Everything the provider's output depends on that this object can see: identity + in-place version of every
-        parameter and buffer of the provider modules, the train / eval flag of every submodule (dropout in the 'FC' adapter)
-        and the grad mode.  None = the provider is an opaque callable with no declared modules: its output cannot be cached.
+    def _providers(self):
+        mods = self._modules
+        return [(n, mods[n]) for n in self._PROVIDER_NAMES if mods.get(n) is not None]
 
-        The reference's handler calls the model once per bag, so this runs per bag (31 us with an exact walk of the learner and
-        adapter per call, round 4: the whole look-ahead hit path is 9 us): the module / tensor lists of every provider module are
-        kept and only their flags and versions are read.  The lists are exact for the structure epoch they were walked in (any
-        parameter / buffer / submodule registration anywhere bumps it: ``_STRUCT_EPOCH``), and are re-walked whenever the key misses,
-        on ``_apply`` and on ``load_state_dict`` besides."""
-        mods = self._provider_modules()
+    def _get_watches(self):
+        """the watches, made on use: a deep copy / pickle drops them, and a model pickled before they existed has none"""
+        ws = self.__dict__.get("_watches")
+        if ws is None:
+            ws = self.__dict__["_watches"] = {n: ModuleWatch() for n in self._PROVIDER_NAMES}
+            ws["mil_encoder"] = ModuleWatch(_encoder_extras)
+        return ws
+
+    def _provider_key(self, exact=False):
+        """Everything the provider's output depends on that this object can see: the grad mode + the stamp of every provider module
+        (identity + in-place version of every parameter and buffer, the train / eval flag of every submodule: dropout in the 'FC'
+        adapter).  None = the provider is an opaque callable with no declared modules: its output cannot be cached.  The reference's
+        handler calls the model once per bag, so this runs per bag: in steady state nothing is walked."""
+        mods = self._providers()
         if not mods:
             return None
-        if not _HOOKS_INSTALLED[0]:
-            _install_structure_hooks()
-        epoch = _STRUCT_EPOCH[0]
-        kept = self._provider_lists
-        key = [torch.is_grad_enabled()]
-        for m in mods:
-            tl = kept.get(id(m))
-            if tl is None or tl[0] is not m or tl[3] != epoch:
-                sub, tensors = self._walk_module(m)
-                # the walk's identity goes into the key (versions alone cannot tell a re-assigned parameter from the old one); it only
-                # changes when the walk really found other objects -- a registration elsewhere in the process re-walks, nothing more
-                same = (tl is not None and tl[0] is m and len(tl[1]) == len(sub) and len(tl[2]) == len(tensors)
-                        and all(a is b for a, b in zip(tl[1], sub)) and all(a is b for a, b in zip(tl[2], tensors)))
-                if not same:
-                    _STRUCT_EPOCH[1] += 1
-                tl = kept[id(m)] = (m, sub, tensors, epoch, tl[4] if same else _STRUCT_EPOCH[1])
-            key.append((id(m), tl[4], tuple(map(_GET_TRAINING, tl[1])), tuple(map(_GET_VERSION, tl[2]))))
-        return tuple(key)
+        ws = self.__dict__.get("_watches") or self._get_watches()
+        return (torch.is_grad_enabled(), *[ws[n].stamp(m, exact) for n, m in mods])
 
-    @property
-    def _tower_lists(self):        # (module, submodules, tensors) of the text tower as last walked, or None
-        tower = getattr(self, "prompt_encoder", None)
-        tl = self._provider_lists.get(id(tower)) if tower is not None else None
-        return None if tl is None else tl[:3]
+    #: plain (non-tensor) attributes of the MIL encoder that change what a forward computes: part of the look-ahead / deferral state
+    _ENC_SCALAR_NAMES = ("keep_ratio", "pooling", "query_pooling", "gated_query", "pred_head", "query_type")
 
-    @_tower_lists.setter
-    def _tower_lists(self, value):   # `= None`: forget every kept provider list (the next key walks exactly)
-        assert value is None
-        self._provider_lists.clear()
-
-    @property
-    def _provider_walks(self):
-        return {k: (v[1], v[2]) for k, v in self._provider_lists.items()}
+    def _eval_state(self, text_features=None, exact=False):
+        """Everything an inference result depends on besides the bag, as (encoder part, version of the text features, the text-feature
+        tensor): the text side's own cache hands out the same tensor object as long as ITS key holds.  The encoder part (hashable; all
+        that ``_defer_key`` takes, without text features) = the stamp of the MIL encoder's watch -- its tensors and flags, the logit
+        scale, the co-attention scale --, the plain attributes of ``_ENC_SCALAR_NAMES`` as this INSTANCE carries them and the
+        zero-shot pooling spec.  The attributes are read from the encoder's ``__dict__``: a name held as a Parameter / submodule
+        (``query_pooling``) is not there, it is in the watch's lists; a value that is no plain scalar enters by its identity (``_ById``
+        keeps it alive).  ``exact``: walk the encoder again (a window is computed, a deferred batch opened)."""
+        enc = self._modules["mil_encoder"]
+        vals = tuple(map(enc.__dict__.get, self._ENC_SCALAR_NAMES))
+        if not _PLAIN.issuperset(map(type, vals)):
+            vals = tuple(v if v.__class__ in _PLAIN else _ById(v) for v in vals)
+        watch = (self.__dict__.get("_watches") or self._get_watches())["mil_encoder"]
+        encoder_part = (watch.stamp(enc, exact, self), vals, self.image_encoder_cfg.get("pooling"))
+        return encoder_part, None if text_features is None else text_features._version, text_features
 
     @staticmethod
-    def _walk_module(m):
-        """(submodules, parameters + buffers) of a module tree, dict order, every object once (nn.Module.parameters() spends
-        ~0.3 ms on a 150-tensor text tower in generator / prefix-string bookkeeping)."""
-        sub, tensors, stack, seen = [], [], [m], set()
-        while stack:
-            x = stack.pop()
-            if id(x) in seen:
-                continue
-            seen.add(id(x))
-            sub.append(x)
-            tensors.extend(t for t in x._parameters.values() if t is not None)
-            tensors.extend(t for t in x._buffers.values() if t is not None)
-            stack.extend(c for c in x._modules.values() if c is not None)
-        return sub, tensors
+    def _same_state(a, b):
+        return a[0] == b[0] and a[1] == b[1] and a[2] is b[2]
 
+    def _defer_key(self, exact=False):
+        """Everything a training-mode output depends on besides the bag: the text side (fixed features: the buffer -- by identity,
+        kept alive -- and its version; a provider: ``_provider_key``), the encoder part of ``_eval_state``, ``self.training``.  None: a
+        text provider this object cannot see into -- such calls are not deferred.  ``exact``: walk the encoder again (a new batch)."""
+        fixed = self._buffers.get("pretrained_text_features")
+        text = self._provider_key() if fixed is None else (_ById(fixed), fixed._version)
+        return None if text is None else (text, self._eval_state(None, exact)[0], self.training)      # [0]: the encoder part
+
+    def _invalidate(self, level):
+        """drop what an event of ``level`` makes stale: the table at ``_FORWARD`` / ``_WEIGHTS`` / ``_STORAGE``"""
+        self._la = None
+        if level >= _WEIGHTS:
+            self._drop_text_cache()
+            for w in self._get_watches().values():
+                w.forget()
+            self._hot.clear()
+        if level >= _STORAGE:
+            self._plans.clear()
+            self._train_plans.clear()
+            self._prepared_text = self._prepared_query = None
+
+    # -- text side -----------------------------------------------------------------------------------------
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .float(): tensors change under the same Parameter objects and versions -- nothing cached survives
         if "_plans" in self.__dict__:            # (not yet there when a parent converts a half-built model)
-            self._drop_text_cache()
-            self._tower_lists = None
-            self._plans.clear()
-            self._hot.clear()
-            self._train_plans.clear()
-            self._prepared_text = self._prepared_query = None
-            self._la = self._la_lists = None
+            self._invalidate(_STORAGE)
         out = super()._apply(fn, *args, **kwargs)
         self._materialise_frozen_prototypes()
         return out
@@ -371,10 +368,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
         if "_plans" in self.__dict__:
-            self._drop_text_cache()
-            self._tower_lists = None
-            self._hot.clear()
-            self._la = self._la_lists = None
+            self._invalidate(_WEIGHTS)
         return out
 
     def compute_text_features_with_coop(self, prompt_learner):
@@ -415,8 +409,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         if key is None:
             return provider()
         if self._text_cache is None or key != self._text_cache_key:
-            self._tower_lists = None                 # a miss re-walks the tower: a swapped parameter object is seen here at the latest
-            key = self._provider_key()
+            key = self._provider_key(exact=True)     # a miss re-walks the providers: a swapped parameter object is seen here at the latest
             feats = provider()
             if feats.requires_grad and feats.grad_fn is not None:
                 # the cached tensor carries the provider's autograd graph: every bag of the step may hang off it, but once
@@ -469,10 +462,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         X2 = VF._bag2d(X)
         N, D = X2.shape
         Qsrc = enc.step_query()                     # a text adapter's output is evaluated once per parameter version, not per bag
-        Q = Qsrc.detach()
-        if Q.dtype != torch.float32 or not Q.is_contiguous():
-            Q = Q.float().contiguous()
-        P = Q.shape[0] - (1 if enc.gated_query else 0)
+        P = Qsrc.shape[0] - (1 if enc.gated_query else 0)
         K = text_features.shape[0]
         if not (1 <= P <= 16 and 1 <= K <= 64 and D % 8 == 0 and D <= 1024):
             return None
@@ -497,10 +487,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         # out, whose own cache follows the query network's parameters).  A query source that is a plain callable gives no key:
         # prepare every call.
         pkey = self._params_key(enc, Qsrc, text_features)
-        Tc, lsc = text_features.detach().float().contiguous(), self.logit_scale.detach().float()
-        Wc = None if W is None else W.detach().float().contiguous()
-        bc = None if b is None else b.detach().float().contiguous()
-        pwc = None if pw is None else pw.detach().float().reshape(-1).contiguous()
+        Q, Tc, lsc, Wc, bc, pwc = self._f32_operands(Qsrc, text_features, W, b, pw)
         plan.run(X2, Q, Tc, lsc, Wc, bc, pwc, outs=outs, params_key=pkey, query_pool_module=qmod)
         sq = enc.__dict__.get("_step_query")
         shared_query = isinstance(enc.Q, torch.Tensor) or (sq is not None and sq[1] is Qsrc)     # (a stochastic query network -- active
@@ -515,6 +502,13 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         else:
             self._hot.pop((D, X2.dtype, X2.device), None)
         return outs["logits"], outs["vhat"], outs["That"]
+
+    def _f32_operands(self, Qsrc, text_features, W, b, pw):
+        """(Q, T, logit scale, W, b, pool weights) as the fused kernels read them: detached, fp32, contiguous; None stays None"""
+        def f32(t):        # (.float() / .contiguous() hand back the tensor itself when there is nothing to convert)
+            return None if t is None else t.detach().float().contiguous()
+        return (f32(Qsrc), f32(text_features), self.logit_scale.detach().float(), f32(W), f32(b),
+                None if pw is None else pw.detach().float().reshape(-1).contiguous())
 
     def _params_key(self, enc, Qsrc, text_features):
         """Key of the (queries, text features) a plan's prepared block was computed from, or None = prepare every call (a query source
@@ -586,20 +580,13 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return self.forward_bags(list(X))
         la = self._la
         if la is not None and la["rows"] and not self.training and not torch.is_grad_enabled():
-            # the evaluation loop's common case first -- a call that a look-ahead window already holds the answer for (the checks are
-            # those of `_lookahead`: the exact item, the exact model state) -- before anything a miss needs is computed
+            # the evaluation loop's common case first -- a call that a look-ahead window already holds the answer for (the exact item,
+            # then the exact model state: `_lookahead_hit`) -- before anything a miss needs is computed
             src = getattr(X, "_vlsa_src", None)
             if src is not None and src[0] is la["rb"] and not ENV_NO_LOOKAHEAD and not self._materialising and self.lookahead_bags > 1:
-                row = la["rows"].get(src[1])
-                if row is not None:
-                    text_features = self._text_features()
-                    if self._same_state(la["state"], self._eval_state(text_features)):
-                        i = src[1]
-                        la["used"] += 1
-                        la["last"] = i
-                        if i >= la["trigger"]:
-                            self._lookahead_extend(la, text_features)
-                        return self._lookahead_row(row, X)
+                hit = self._lookahead_hit(la, src[1], X)
+                if hit is not None:
+                    return hit
         pc = self._pending_calls
         if (pc is not None and self.defer_training_calls and not ENV_NO_DEFER and not self._materialising and self.training
                 and torch.is_grad_enabled()):
@@ -623,7 +610,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             if fused is not None:
                 return fused
         else:
-            self._la = None                      # a differentiable forward: parameters are about to move
+            self._invalidate(_FORWARD)           # a differentiable forward: parameters are about to move
             if self.defer_training_calls and not ENV_NO_DEFER and self.training and not self._materialising:
                 deferred = self._defer_call(X, text_features)
                 if deferred is not None:
@@ -643,9 +630,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             That, _ = VF.normalize_rows(text_features.detach())
             h = VF.head_forward(feats, "given", None, None, None, That, self.logit_scale.detach())
             return h["logits"][None, :], h["vhat"][None, :], That
-        if (feats.is_cuda and feats.dim() == 2 and feats.shape[0] == 1 and feats.dtype == torch.float32 and feats.shape[1] % 4 == 0
-                and feats.shape[1] <= 1024 and text_features.is_cuda and text_features.dim() == 2 and 1 <= text_features.shape[0] <= 64
-                and text_features.shape[1] == feats.shape[1] and self.logit_scale.is_cuda):
+        if feats.dim() == 2 and feats.shape[0] == 1 and self._train_head_takes(feats, text_features):
             # any encoder, gradient needed: both normalisations and the cosine logits as ONE autograd node (two launches each way:
             # the batched training head with B = P = 1 and an identity adapter) instead of ~12 torch ops and as many backward
             # nodes -- the bag-by-bag training loop is bound by those
@@ -658,50 +643,6 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         return logits, image_features, text_features
 
     # -- deferred training calls: the reference handler's bag-by-bag TRAINING loop at batched speed (vlsa_amd/deferred.py) -------
-    #: plain (non-tensor) attributes of the MIL encoder that change what a forward computes (``_ENC_SCALAR_NAMES``) are part of the
-    #: look-ahead / deferral state
-
-    def _encoder_lists(self):
-        """(encoder, its submodules, its tensors + logit scale, structure epoch): kept between calls, re-walked when the encoder
-        object changed, when ANY module registered a parameter / buffer / submodule since (``_STRUCT_EPOCH``: a re-assigned
-        ``enc.Q = nn.Parameter(...)`` is seen at the next call), on ``_apply``, ``load_state_dict`` and before every window / batch."""
-        if not _HOOKS_INSTALLED[0]:
-            _install_structure_hooks()
-        ll = self._la_lists
-        enc = self._modules["mil_encoder"]
-        if ll is None or ll[0] is not enc or ll[3] != _STRUCT_EPOCH[0]:
-            sub, tensors = self._walk_module(enc)
-            tensors = tensors + [self._parameters["logit_scale"]]
-            cs = getattr(enc, "coattn_logit_scale", None)
-            if isinstance(cs, torch.Tensor):
-                tensors.append(cs)
-            ll = self._la_lists = (enc, sub, tensors, _STRUCT_EPOCH[0])
-        return ll
-
-    _ENC_SCALAR_NAMES = ("keep_ratio", "pooling", "query_pooling", "gated_query", "pred_head", "query_type")
-
-    def _encoder_scalars(self, enc):
-        """the plain attributes of ``_ENC_SCALAR_NAMES`` as this INSTANCE carries them (read from its ``__dict__``: a name held as a
-        Parameter / submodule -- ``query_pooling`` -- is not there; it is in the tensor / module lists, compared by identity)"""
-        d = enc.__dict__
-        return (tuple([d.get(n) for n in self._ENC_SCALAR_NAMES]), self.image_encoder_cfg.get("pooling"))
-
-    def _defer_key(self):
-        """Everything a training-mode output depends on besides the bag: the text side (fixed features: the buffer's version; a
-        provider: its modules' tensors / flags, ``_provider_key``), the MIL encoder's tensors and flags, the logit scale.  None: a
-        text provider this object cannot see into -- such calls are not deferred."""
-        fixed = self._buffers.get("pretrained_text_features") if "pretrained_text_features" in self._buffers else None
-        pk = None
-        if fixed is None:
-            pk = self._provider_key()
-            if pk is None:
-                return None
-        ll = self._encoder_lists()
-        sc, zs = self._encoder_scalars(ll[0])
-        sc = tuple(v if v.__class__ in _PLAIN else id(v) for v in sc)       # (a Parameter / module as pooling spec: its identity)
-        return (pk, None if fixed is None else (id(fixed), fixed._version), tuple(map(_GET_VERSION, ll[2])), tuple(map(_GET_TRAINING, ll[1])),
-                self.training, (sc, zs))
-
     def _defer_call(self, X, text_features):
         from .deferred import TrainingCalls
         if not (TrainingCalls.takes(X) and text_features.dim() == 2):
@@ -716,19 +657,14 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return None                                      # an encoder this package does not know: no claim about its output shape
         pc = self._pending_calls
         if pc is None or not pc.same_state():
-            self._la_lists = None                           # an exact walk of the encoder for the batch's key
-            key = self._defer_key()
+            key = self._defer_key(exact=True)                # an exact walk of the encoder for the batch's key
             if key is None:
                 return None
-            # every module / tensor of the model from the walks the key was just built from (text-side modules: `_provider_walks`
-            # + the kept tower lists; the encoder: `_la_lists`) -- no second walk over the ~120 modules of the tower
-            sub, tensors = list(self._la_lists[1]), list(self._la_lists[2])
-            if key[0] is not None:
-                walks = self._provider_walks
-                for m in self._provider_modules():
-                    w = walks.get(id(m)) or self._walk_module(m)
-                    sub += w[0]
-                    tensors += w[1]
+            # every module / tensor of the model from the walks the key was just built from (the encoder's watch; the providers'
+            # when the text side runs per step) -- no second walk over the ~120 modules of the tower
+            ws = self._get_watches()
+            names = ["mil_encoder"] + ([n for n, _ in self._providers()] if self._buffers.get("pretrained_text_features") is None else [])
+            sub, tensors = [x for n in names for x in ws[n].lists()[0]], [t for n in names for t in ws[n].lists()[1]]
             if any(isinstance(m, nn.modules.dropout._DropoutNd) and m.p > 0 and m.training for m in sub):
                 return None                                  # per-call random masks: every call is its own evaluation
             pc = self._pending_calls = TrainingCalls(self, key, [t for t in tensors if t.requires_grad], text_features.shape[0],
@@ -760,24 +696,21 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         return err
 
     # -- look-ahead: the reference handler's bag-by-bag evaluation loop at batched speed ---------------------------------------
-    def _eval_state(self, text_features):
-        """Everything an inference result depends on besides the bag: the text-feature tensor (object + in-place version: the text
-        side's own cache hands out the same object as long as ITS key -- every provider tensor's version and flags -- holds) and
-        every parameter / buffer (object + version) and train / eval flag of the MIL encoder (query network included), the logit
-        scale, the co-attention scale.  The module / tensor lists are kept between calls and rebuilt by an exact walk whenever a
-        window is computed, on ``_apply`` and on ``load_state_dict``."""
-        ll = self._encoder_lists()
-        return (ll[2], tuple(map(_GET_VERSION, ll[2])), tuple(map(_GET_TRAINING, ll[1])), text_features, text_features._version,
-                self._encoder_scalars(ll[0]))
-
-    @staticmethod
-    def _same_state(a, b):
-        try:       # (a[5]: plain attribute values; a Parameter / module among them compares by identity first -- two DIFFERENT tensors
-            same_scalars = a[5] == b[5]        # there would make `==` elementwise: that is simply "not the same state")
-        except RuntimeError:
-            same_scalars = False
-        return (same_scalars and a[1] == b[1] and a[2] == b[2] and a[3] is b[3] and a[4] == b[4]
-                and (a[0] is b[0] or (len(a[0]) == len(b[0]) and all(x is y for x, y in zip(a[0], b[0])))))
+    def _lookahead_hit(self, la, i, X, text_features=None):
+        """the row of item i if la's windows hold it and the model state they were computed under still holds, else None.  The order
+        -- row present, then text features, then state -- is what makes a hit cheap."""
+        row = la["rows"].get(i)
+        if row is None:
+            return None
+        if text_features is None:
+            text_features = self._text_features()
+        if not self._same_state(la["state"], self._eval_state(text_features)):
+            return None
+        la["used"] += 1
+        la["last"] = i
+        if i >= la["trigger"]:
+            self._lookahead_extend(la, text_features)
+        return self._lookahead_row(row, X)
 
     def _lookahead(self, src, X, text_features):
         """``net(X)`` in eval mode under ``no_grad`` for item i of a ``ResidentBags`` dataset (the handler's ``test_model`` loop,
@@ -791,17 +724,12 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         forward, ``_apply`` or ``load_state_dict`` drops the windows.  An access pattern that does not use its windows shrinks
         them (random access degenerates to the per-bag route)."""
         rb, i = src
-        state = self._eval_state(text_features)
         la = self._la
         same_rb = la is not None and la["rb"] is rb
-        if same_rb and la["rows"] and self._same_state(la["state"], state):
-            row = la["rows"].get(i)
-            if row is not None:
-                la["used"] += 1
-                la["last"] = i
-                if i >= la["trigger"]:
-                    self._lookahead_extend(la, text_features)
-                return self._lookahead_row(row, X)
+        if same_rb and la["rows"]:
+            hit = self._lookahead_hit(la, i, X, text_features)
+            if hit is not None:
+                return hit
         width, seq = int(self.lookahead_bags), 0
         if same_rb:
             width, seq = la["width"], la["seq"]
@@ -821,8 +749,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         Xp = X.as_subclass(torch.Tensor)
         if first is None or first.data_ptr() != Xp.data_ptr() or tuple(first.shape) != tuple(Xp.shape[-2:]):
             return None                               # not (yet) the resident rows: the per-bag route
-        self._la_lists = None                         # the kept lists are re-walked exactly before a window is computed
-        la["state"] = self._eval_state(text_features)
+        la["state"] = self._eval_state(text_features, exact=True)      # the encoder is walked exactly before a window is computed
         if self._lookahead_window(la, text_features, width) < 2 and not la["rows"]:
             return None
         la["used"] = 1
@@ -882,8 +809,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         last = la["last"]
         for j in [j for j in la["rows"] if j < last]:
             del la["rows"][j]
-        self._la_lists = None
-        state = self._eval_state(text_features)
+        state = self._eval_state(text_features, exact=True)
         if not self._same_state(la["state"], state):
             return
         la["state"] = state
@@ -914,9 +840,8 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         if ret_with_attn:
             return self._forward_bags_attn(bags, text_features)
         if self._needs_grad(text_features):
-            self._la = None                      # a differentiable forward: parameters are about to move (see _lookahead)
-            if (isinstance(enc, VLFAN) and len(bags) > 0 and all(x.is_cuda and x.shape[-1] == 512 and x.shape[-2] > 0 for x in bags)
-                    and all(x.dtype == bags[0].dtype for x in bags)):
+            self._invalidate(_FORWARD)           # a differentiable forward: parameters are about to move (see _lookahead)
+            if isinstance(enc, VLFAN) and _device_bags_512(bags):
                 spec = enc.fused_head_spec()
                 if (spec is not None and spec[0] == "mean" and text_features.is_cuda and text_features.shape[0] <= 64
                         and text_features.shape[1] == 512):
@@ -962,12 +887,15 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         feats = [VF.normalize_many(x) for x in flat] if getattr(self, "return_patch_features", None) is True else None
         return logits, feats, outs[0][1]
 
+    def _train_head_takes(self, feats, T):
+        """whether bag vectors [B, C] and text features T go through the one-node training head (``VF.head_train`` with P = 1)"""
+        return (feats.is_cuda and feats.dtype == torch.float32 and feats.shape[1] % 4 == 0 and feats.shape[1] <= 1024 and T.is_cuda
+                and T.dim() == 2 and 1 <= T.shape[0] <= 64 and T.shape[1] == feats.shape[1] and self.logit_scale.is_cuda)
+
     def _deepmil_logits(self, feats, text_features):
         """cosine logits of a DeepMIL batch's bag vectors [B, C], as the per-bag ``forward`` forms them: both normalisations and the
         logits as ONE autograd node (the batched training head with P = 1) where it applies, torch ops otherwise"""
-        if (feats.is_cuda and feats.dtype == torch.float32 and feats.shape[1] % 4 == 0 and feats.shape[1] <= 1024 and text_features.is_cuda
-                and text_features.dim() == 2 and 1 <= text_features.shape[0] <= 64 and text_features.shape[1] == feats.shape[1]
-                and self.logit_scale.is_cuda):
+        if self._train_head_takes(feats, text_features):
             return VF.head_train(feats.unsqueeze(1).contiguous(), None, None, text_features, self.logit_scale, self._head_tickets)
         text_n = F.normalize(text_features, dim=-1)
         image_features = F.normalize(feats.float(), dim=-1)
@@ -985,8 +913,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         grad = self._needs_grad(text_features)
         spec = enc.fused_head_spec()
         flat = [VF._bag2d(x) for x in bags]
-        ok = (len(flat) > 0 and all(x.is_cuda and x.dtype == flat[0].dtype and x.shape[1] == 512 and x.shape[0] > 0 for x in flat))
-        if grad or spec is None or spec[0] == "module" or not ok:
+        if grad or spec is None or spec[0] == "module" or not _device_bags_512(flat):
             with torch.set_grad_enabled(grad):
                 text_n = F.normalize(text_features, dim=-1)
                 feats, attn = enc.forward_bags(bags, ret_with_attn=True)
@@ -1011,11 +938,9 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             flat = enc.feat_proj.forward_bags(flat)    # use_feat_proj=True: one fused HIP launch per 64 bags, fp32 [N, 512] out
             projected = True
         ok = (spec is not None and spec[0] != "module" and len(flat) > 0
-              and ((trusted and not projected)
-                   or all(x.is_cuda and x.dtype == flat[0].dtype and x.shape[1] == 512 and x.shape[0] > 0 for x in flat)))
+              and ((trusted and not projected) or _device_bags_512(flat)))
         if not ok:
-            same = (len(flat) > 0 and all(x.is_cuda and x.dtype == flat[0].dtype and x.shape[1] == 512 and x.shape[0] > 0 for x in flat)
-                    and flat[0].dtype in (torch.bfloat16, torch.float32))
+            same = _device_bags_512(flat) and flat[0].dtype in (torch.bfloat16, torch.float32)
             if same and isinstance(enc, FeatMIL) and enc.pooling not in ("mean", "max") and text_features.shape[0] <= 64:
                 return self._forward_bags_zeroshot(flat, text_features)
             if same and isinstance(enc, FeatMIL) and enc.pooling in ("mean", "max"):
@@ -1033,8 +958,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
                 return self.logit_scale.exp() * feats @ That.t(), feats, That
             if same and isinstance(enc, mil_encoders.DeepMIL) and (enc.feat_proj is None or projected):
                 return self._forward_bags_deepmil(flat, text_features)
-            if (isinstance(enc, VLFAN) and (enc.feat_proj is None or projected) and len(flat) > 0
-                    and all(x.is_cuda and x.dtype == flat[0].dtype and x.shape[1] == 512 and x.shape[0] > 0 for x in flat)):
+            if isinstance(enc, VLFAN) and (enc.feat_proj is None or projected) and _device_bags_512(flat):
                 # pooling over the queries by a module (attention / gated attention): batched HIP aggregation, then the
                 # module, the adapter and the cosine logits as batched torch ops on [B, P, 512]
                 That = F.normalize(text_features, dim=-1)
@@ -1044,18 +968,11 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), outs[0][2]
         mode, pw, W, b = spec
         Qsrc = enc.step_query()
-        Q = Qsrc.detach()
-        if Q.dtype != torch.float32 or not Q.is_contiguous():
-            Q = Q.float().contiguous()
+        Q, T, ls, Wc, bc, pwc = self._f32_operands(Qsrc, text_features, W, b, pw)
         pkey = self._params_key(enc, Qsrc, text_features) if isinstance(Qsrc, torch.Tensor) else None
         P = Q.shape[0] - (1 if enc.gated_query else 0)
         K = text_features.shape[0]
-        T = text_features.detach().float().contiguous()
-        ls = self.logit_scale.detach().float()
         logits, feats, That, used = [], [], None, []
-        Wc = None if W is None else W.detach().float().contiguous()
-        bc = None if b is None else b.detach().float().contiguous()
-        pwc = None if pw is None else pw.detach().float().reshape(-1).contiguous()
         # bags per persistent launch: 64 x 50k-patch bags are 3.3 GB per launch already; slide-sized bags (the reference's TCGA bags:
         # 2-12k patches) go up to the forward kernels' 256 per launch -- the launch's fixed latency chain and the host calls are
         # paid per launch (2 798-patch bags: 0.62 -> 0.47 us per bag in the streaming kernel)
