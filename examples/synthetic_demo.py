@@ -7,7 +7,8 @@
      `VLSA.forward_bags` (persistent multi-bag HIP kernels)
   3. a few optimizer steps through `TrainStep`: text tower once per step, batched HIP forward + backward of the aggregation, IF-MLE +
      EMD objective in one kernel, one-launch Adam on the context / rank embeddings, the text queries' residual and the logit scale; a
-     batch that repeats is replayed as one hipGraph
+     batch that repeats is replayed as one hipGraph; the evaluation pass before and after is scored on the device (`SurvEvaluator`:
+     Harrell's C and the losses from the logits in two launches and one 128-byte copy)
   4. interpretation of one slide (`calc_text_img_similarity`)
 
     python examples/synthetic_demo.py [--patients 64] [--steps 5]
@@ -25,7 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from vlsa_amd.inference import calc_text_img_similarity  # noqa: E402
 from vlsa_amd.ingest import ArenaLayout, DeviceBagArena  # noqa: E402
-from vlsa_amd.losses import SurvObjective  # noqa: E402
+from vlsa_amd.evaluate import SurvEvaluator  # noqa: E402
+from vlsa_amd.losses import SurvEMD, SurvIFMLE, SurvObjective  # noqa: E402
 from vlsa_amd.optim import FusedAdam  # noqa: E402
 from vlsa_amd.prompt_adapter import PromptAdapter  # noqa: E402
 from vlsa_amd.prompt_encoder import CONCHPromptEncoder  # noqa: E402
@@ -112,6 +114,17 @@ def main():
     t_bin = torch.randint(0, K, (len(pids),), generator=g).to(dev)
     event = (torch.rand(len(pids), generator=g) < 0.5).float().to(dev)
     objective = SurvObjective()
+    # the handler's _eval_and_print (runner/vlsa_handler.py:291-313) without the logits leaving the device
+    evaluator, labels = SurvEvaluator("incidence"), torch.stack([t_bin.float(), event], dim=1)
+    ext_losses = {"SurvIFMLE": SurvIFMLE(), "SurvEMD": SurvEMD()}
+
+    def score(phase, raw_pred):
+        res = evaluator.compute({"y": labels, "raw_y_hat": raw_pred, "uid": pids}, ["c_index", "loss"], kws_ext_loss=ext_losses,
+                                loss_weight={"SurvIFMLE": 1.0, "SurvEMD": 1.0}, logit_scale=net.get_logit_scale().detach())
+        print(f"[score]  {phase}: c_index {res['c_index']:.4f} ({evaluator.counts['comparable']} comparable pairs), "
+              + ", ".join(f"{k} {v:.4f}" for k, v in res.items() if k != "c_index"))
+
+    score("before training", logits)
     trainable = [p for p in net.parameters() if p.requires_grad]
     # the handler's optimizer (optim_factory.py:25-37: no weight decay on 1-D parameters) as ONE launch; the step itself owned by TrainStep:
     # a batch seen for the third time is replayed as one hipGraph (forward_bags, objective, backward, Adam)
@@ -135,8 +148,12 @@ def main():
     stepper.check_epoch()                                                  # the last epoch's gather status (set_epoch reads the earlier ones)
     print(f"[train]  {stepper.describe()}")
 
-    # 4. interpretation -----------------------------------------------------------------------------------------------
     net.eval()
+    with torch.no_grad():
+        logits = torch.cat([net.forward_bags(bags)[0] for bags in arena.batches(pids, 32)])
+    score("after training ", logits)
+
+    # 4. interpretation -----------------------------------------------------------------------------------------------
     _, A, cottn, probs, probs2, dec, shap = calc_text_img_similarity(net, arena.bag(pids[0])[None])
     print(f"[interp] attention {tuple(A.shape)}, incidence {probs.numpy().round(3).tolist()}, prototype SHAP sum {shap.sum().item():+.4f}")
     print("demo ok")

@@ -580,6 +580,57 @@ int vlsa_surv_objective(const float* x, const int64_t* t, const float* e, int B,
                         float* objective, float* grad, void* stream);
 
 /*
+ * Scoring a split on the device: what NLLSurv_Evaluator (eval/evaluator_surv.py:45-235, backend other than SurvivalEVAL) computes on
+ * the host from the [M, K] predictions of a pass -- in two launches and one 128-byte result buffer.
+ *
+ * vlsa_surv_eval_rows: per-sample work, EVERYTHING in float64 (converter, cumsum / cumprod, logs, sums; one workgroup, fixed order of
+ * every sum: two runs give the same bits).  1 <= M <= VLSA_EVAL_MAX_M (VLSA_EUNSUPPORTED above), 1 <= K <= VLSA_MAX_K.
+ *   x [M, K] fp32  raw logits (x_kind = VLSA_EVAL_RAW: the handler's converter utils/func.py:43-46 is fused in, softmax for
+ *                  pred_type = VLSA_EVAL_INCIDENCE, sigmoid for VLSA_EVAL_HAZARD) or converted predictions (VLSA_EVAL_CONVERTED)
+ *   t int64 bin (clamped to [0, K - 1] where it indexes), e fp32 (!= 0: event)
+ *   alpha, eps     of the evaluator's loss_mle (SurvIFMLE / SurvMLE, loss/loss_surv.py:104-169); loss_mle_org is alpha = 0
+ *   ext_mask       bit 0: the handler's SurvIFMLE (ext_alpha, ext_eps), bit 1: its SurvEMD (p in {1, 2}, raw_distance; logit scale =
+ *                  logit_scale[0] on the device, or logit_scale_value where that pointer is NULL; exponentiated here where
+ *                  ls_is_log != 0) -- incidence only (VLSA_EUNSUPPORTED otherwise), weighted by w_ifmle / w_emd
+ *   est [M]        out: -sum_k S_k, S = 1 - cumsum(incidence) or cumprod(1 - hazard), unclamped (eval/cindex.py:36-43)
+ *   time [M]       out: (double) t
+ *   surv [M, K]    out, may be NULL: S clamped at 0 (eval/evaluator_surv.py:110-116), fp32
+ *   result [VLSA_EVAL_RESULT_WORDS] 8-byte words: doubles at VLSA_EVAL_SUM_MLE .. VLSA_EVAL_M -- sums over the samples of loss_mle,
+ *                  loss_mle_org, w_ifmle * SurvIFMLE, w_emd * SurvEMD; the number of events, of non-finite est, and M -- and the five
+ *                  uint64 pair counters at VLSA_EVAL_CONCORDANT .., which this launch ZEROES
+ * vlsa_concordance_pairs: scikit-survival's concordance_index_censored counts (eval/cindex.py:86-150) of any estimate: for every i
+ * with an event, the j with time_j > time_i or (time_j == time_i and j censored) are comparable; of those a pair is tied when
+ * |est_j - est_i| <= tied_tol, concordant when est_j < est_i and not tied, discordant otherwise.
+ *   counters [5] uint64: concordant, discordant, tied_risk, tied_time, comparable -- ADDED to (zero_first != 0: a hipMemsetAsync
+ *   node zeroes them first; pass &result[VLSA_EVAL_CONCORDANT] and 0 behind vlsa_surv_eval_rows).  Integer sums: identical counts
+ *   from run to run and under any permutation of the samples.  1 <= M <= VLSA_EVAL_MAX_M.
+ */
+#define VLSA_EVAL_INCIDENCE 0
+#define VLSA_EVAL_HAZARD 1
+#define VLSA_EVAL_RAW 0
+#define VLSA_EVAL_CONVERTED 1
+#define VLSA_EVAL_MAX_M 65536
+#define VLSA_EVAL_RESULT_WORDS 16
+#define VLSA_EVAL_SUM_MLE 0
+#define VLSA_EVAL_SUM_MLE_ORG 1
+#define VLSA_EVAL_SUM_IFMLE 2
+#define VLSA_EVAL_SUM_EMD 3
+#define VLSA_EVAL_EVENTS 4
+#define VLSA_EVAL_NONFINITE 5
+#define VLSA_EVAL_M 6
+#define VLSA_EVAL_CONCORDANT 8
+#define VLSA_EVAL_DISCORDANT 9
+#define VLSA_EVAL_TIED_RISK 10
+#define VLSA_EVAL_TIED_TIME 11
+#define VLSA_EVAL_COMPARABLE 12
+int vlsa_surv_eval_rows(const float* x, int x_kind, int pred_type, const int64_t* t, const float* e, int M, int K, double alpha,
+                        double eps, const float* logit_scale, double logit_scale_value, int ls_is_log, int ext_mask, double ext_alpha,
+                        double ext_eps, int p, int raw_distance, double w_ifmle, double w_emd, double* est, double* time, float* surv,
+                        double* result, void* stream);
+int vlsa_concordance_pairs(const double* time, const float* e, const double* est, int M, double tied_tol, uint64_t* counters,
+                           int zero_first, void* stream);
+
+/*
  * The optimizer of the training step in ONE launch: torch.optim.Adam's update (runner/vlsa_handler.py:283-289 builds
  * optim.Adam(lr, weight_decay) through optim_factory.py:25-60; amsgrad = False, maximize = False, L2 weight decay added to the
  * gradient) over n_tensors fp32 tensors.  tensors: HOST array (read during the call: by-value kernel arguments); hyper: DEVICE float

@@ -5,7 +5,7 @@ in hand-written HIP kernels behind the C ABI of include/vlsa_hip.h.  There is no
 """
 from ._native import VlsaNativeError  # noqa: F401
 
-__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA"]
+__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA", "SurvEvaluator", "concordance_index_censored", "concordance_counts"]
 
 
 def __getattr__(name):
@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "ILRA":
         from .deepmil import ILRA
         return ILRA
+    if name in ("SurvEvaluator", "concordance_index_censored", "concordance_counts"):
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
