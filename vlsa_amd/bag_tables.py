@@ -79,6 +79,14 @@ def bag_rows(bags, D=None, empty_stride=None) -> np.ndarray:
     return np.asarray(rows, dtype=np.int64).reshape(len(rows), 3)
 
 
+def _fits(x, D: int, dtype, device, non_empty: bool) -> bool:
+    """THE per-bag condition of the batched routes: [N, D] or [1, N, D], the dtype and device of the first bag (whose dtype the caller
+    has found among bf16 / fp32), N >= 1 where asked.  (One ``shape`` per bag: a list of 64 bags pays this per bag.)"""
+    s = x.shape
+    return ((len(s) == 2 or (len(s) == 3 and s[0] == 1)) and s[-1] == D and x.dtype == dtype and x.device == device
+            and (s[-2] >= 1 or not non_empty))
+
+
 def checked_bags(bags, D: int, message: str, non_empty: bool = False, no_grad: Optional[str] = None) -> list:
     """Every bag on the GPU and through ``_bag2d``; all of width D, one dtype (bf16 or fp32) and one device -- else
     ``VlsaNativeError(message)``.  non_empty: N_i >= 1 as well.  no_grad: the message for a bag that requires grad while grad is
@@ -86,14 +94,63 @@ def checked_bags(bags, D: int, message: str, non_empty: bool = False, no_grad: O
     keep = []
     for x in bags:
         _need_gpu(x)
-        x = _bag2d(x)
-        if (x.shape[1] != D or (non_empty and x.shape[0] < 1)
-                or (keep and (x.dtype != keep[0].dtype or x.device != keep[0].device))):
+        x = _bag2d(x)                       # (bf16 or fp32 behind it: other dtypes come out as fp32 copies)
+        first = keep[0] if keep else x
+        if not _fits(x, D, first.dtype, first.device, non_empty):
             raise VlsaNativeError(message)
         if no_grad is not None and torch.is_grad_enabled() and x.requires_grad:
             raise VlsaNativeError(no_grad)
         keep.append(x)
     return keep
+
+
+def is_bag_set(bags) -> bool:
+    """a ``functional.BagSet`` (which imports this module): checked bags with their ``sizes`` and kept ``chunk`` sub-sets"""
+    return hasattr(bags, "sizes") and hasattr(bags, "chunk")
+
+
+def uniform_bags(bags, D: int = 512) -> bool:
+    """``checked_bags(bags, D, ..., non_empty=True)`` without raising and without converting: whether the batched routes take these
+    bags as they are -- a ``BagSet`` of width D (checked when it was built), or a non-empty sequence of device tensors [N >= 1, D]
+    or [1, N, D] of one dtype (bf16 or fp32) on one device.  A gradient of the bags is the caller's question."""
+    if is_bag_set(bags):
+        return bags.D == D
+    if len(bags) == 0:
+        return False
+    dtype, device = bags[0].dtype, bags[0].device
+    return dtype in _BAG_DTYPES and all(x.is_cuda and _fits(x, D, dtype, device, True) for x in bags)
+
+
+def bag_chunks(bags, n: int = 64, max_rows: Optional[int] = None):
+    """The chunks of <= n bags a batched route launches on, in order.  A ``BagSet`` hands out ``bags.chunk(i, n)`` -- itself when it
+    fits, else its kept sub-sets, each with its device-side table; a list (or the ``ProjectedBags`` of one chunk) goes out as it is
+    when it fits and as slices otherwise.  max_rows: a chunk also closes before the bag that would take it past ``max_rows`` rows, and
+    a bigger bag travels alone."""
+    B, is_set = len(bags), is_bag_set(bags)
+    if max_rows is None:
+        if is_set:
+            for i in range(0, B, n):
+                yield bags.chunk(i, n)
+        elif 0 < B <= n:
+            yield bags
+        else:
+            for i in range(0, B, n):
+                yield bags[i:i + n]
+        return
+    sizes = bags.sizes if is_set else [int(x.shape[0]) for x in bags]
+    i = 0
+    while i < B:
+        j, rows = i + 1, sizes[i]
+        while j < B and j - i < n and rows + sizes[j] <= max_rows:
+            rows += sizes[j]
+            j += 1
+        yield bags.chunk(i, j - i) if is_set else (bags if j - i == B else bags[i:j])
+        i = j
+
+
+def cat(parts):
+    """the results of a route's chunks as one tensor: the only one as it is"""
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def merge_strides(G: int, P: int, D: int, out=None):

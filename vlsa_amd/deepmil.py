@@ -12,6 +12,7 @@ The reference picks the encoder with ``getattr(model.deepmil, cfg['name'])(**cfg
 """
 from __future__ import annotations
 
+import collections
 import math
 
 import torch
@@ -309,34 +310,57 @@ class VLFAN(VF.nat.TransientCaches, nn.Module):
         Q = self.get_query()
         scale = self.coattn_scale()
         outs, attn = [], []
-        is_set = isinstance(bags, VF.BagSet)        # checked once, descriptor rows kept: sub-sets stay BagSets
-        for i in range(0, len(bags), 64):
-            r = VF.vlfan_cross_attention_bags(bags.chunk(i, 64) if is_set else bags[i:i + 64], Q, gated=self.gated_query, coattn_scale=scale,
-                                              want_attn=ret_with_attn)
+        for chunk in VF.bag_chunks(bags):           # (a BagSet's sub-sets stay BagSets: checked once, descriptor rows kept)
+            r = VF.vlfan_cross_attention_bags(chunk, Q, gated=self.gated_query, coattn_scale=scale, want_attn=ret_with_attn)
             if ret_with_attn:
                 outs.append(r[0])
                 attn.extend(a.unsqueeze(0) for a in r[1])
             else:
                 outs.append(r)
-        return (outs[0] if len(outs) == 1 else torch.cat(outs)), attn
+        return VF.cat(outs), attn
 
 
-def _batch_pools(flat) -> bool:
-    """whether the batched max / mean pooling takes these [N_i, C] bags: device tensors of width 512 and one dtype (bf16 or fp32), none empty"""
-    return (len(flat) > 0 and flat[0].dtype in (torch.bfloat16, torch.float32)
-            and all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == flat[0].dtype for x in flat))
+def pool_mean_max(flat, mode: str, bag_grad: bool = False, join=VF.cat) -> torch.Tensor:
+    """'mean' / 'max' pooling [B, C] of a list of [N_i, C] bags, for DeepMIL and FeatMIL (model/deepmil.py:57-60,271-274 per bag).
+    Bags the batched kernels take (``uniform_bags``): VF.mean_pool_bags / VF.max_pool_bags per <= 64 bags -- under a bag gradient one
+    autograd node per chunk -- except ONE bag's max without a gradient, which is the single-bag launch pair's.  Anything else bag by
+    bag: torch ops under a bag gradient and on CPU tensors, the single-bag launch pair otherwise.  bag_grad: the caller differentiates
+    through the bags (``forward_bags``; the routes without autograd say no).  join: what makes one tensor of the chunks' results."""
+    if VF.uniform_bags(flat) and (mode == "mean" or bag_grad or len(flat) > 1):
+        pool = VF.mean_pool_bags if mode == "mean" else VF.max_pool_bags
+        return join([pool(chunk) for chunk in VF.bag_chunks(flat)])
+    if mode == "mean":
+        return torch.stack([x.float().mean(dim=0) if (bag_grad or not x.is_cuda) else VF.scored_pool(x, None) for x in flat])
+    return torch.stack([x.float().amax(dim=0) if (bag_grad or not x.is_cuda) else VF.colmax(x) for x in flat])
 
 
-def _pool_chunks(flat, pool):
-    """``pool`` (VF.max_pool_bags / VF.mean_pool_bags) over the bags in chunks of 64; a ``BagSet`` or the projected bags of one chunk go
-    in as they are, with their device-side table"""
-    if len(flat) <= 64:
-        return pool(flat)
-    is_set = isinstance(flat, VF.BagSet)
-    return torch.cat([pool(flat.chunk(i, 64) if is_set else flat[i:i + 64]) for i in range(0, len(flat), 64)])
+def _device_bag(X2) -> bool:
+    """one bag the fused score kernels read: bf16 or fp32 device rows, at least one"""
+    return X2.is_cuda and X2.dtype in (torch.bfloat16, torch.float32) and X2.shape[0] > 0
 
 
-class DeepMIL(VF.nat.TransientCaches, nn.Module):
+class _DropoutSeed:
+    """nn.Module mixin: the seed words of the batched training forwards whose dropout masks are drawn inside the kernels"""
+
+    def _dropout_seed_word(self, device) -> torch.Tensor:
+        """The seed of one batched training forward as a device word: a per-module device counter, its base drawn ONCE from torch's CPU
+        generator (``torch.manual_seed`` governs it), advanced in-stream by every call -- eagerly and in a captured graph's replays
+        alike -- and snapshotted, so that the backward of this call reads the seed its forward read."""
+        ctr = self.__dict__.get("_drop_counter")
+        if ctr is None or ctr.device != device:
+            base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            ctr = self._drop_counter = torch.full((1,), base, dtype=torch.int64, device=device)
+        ctr.add_(1)
+        return ctr.clone()
+
+
+# what DeepMIL's four routes read of its pooling module: gated; the three Linear layers; weights: the six tensors the kernels take;
+# drop_p: the ACTIVE dropout rate (0.0 in eval and for the ungated module); rates_equal: both branches drop at one rate (the kernels
+# draw one mask rate); widths_fused: 512 -> 256, the fused score kernels' sizes
+_PoolSpec = collections.namedtuple("_PoolSpec", "gated lin_a lin_g lin_o weights drop_p rates_equal widths_fused")
+
+
+class DeepMIL(VF.nat.TransientCaches, _DropoutSeed, nn.Module):
     """ABMIL-style encoder (model/deepmil.py:222-292): optional Feat_Projecter, mean / max / (gated-)attention pooling
     over the N patches, Adapter head mixed with ``keep_ratio`` or a Linear head."""
 
@@ -368,44 +392,60 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
         (512 -> 256 hidden, no active dropout), otherwise bag by bag.  model/deepmil.py:270-283 per bag."""
         sg = self.sigma
         if isinstance(sg, str):
-            if sg == "mean" and len(flat) > 0 and all(x.is_cuda and x.shape[1] == 512 and x.shape[0] > 0
-                                                      and x.dtype == flat[0].dtype for x in flat):
-                return torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
-            if sg == "max" and len(flat) > 1 and _batch_pools(flat):
-                return _pool_chunks(flat, VF.max_pool_bags)
-            return torch.stack([VF.scored_pool(x, None) if sg == "mean" else VF.colmax(x) for x in flat])
-        gated = isinstance(sg, Gated_Attention_Pooling)
-        lin_a = sg.fc1[0] if gated else sg.attention[0]
-        if (not (gated and sg.training and sg.fc1[2].p > 0) and len(flat) > 0
-                and all(VF.FusedAttnScores.supported(x, lin_a.in_features, lin_a.out_features) for x in flat)):
-            if not hasattr(self, "_fused_scores"):
-                self._fused_scores = VF.FusedAttnScores()
-            w = ((lin_a.weight, lin_a.bias, sg.score[0].weight, sg.score[0].bias, sg.fc2.weight, sg.fc2.bias) if gated else
-                 (lin_a.weight, lin_a.bias, None, None, sg.attention[2].weight, sg.attention[2].bias))
-            return torch.cat([self._fused_scores.pool_bags(flat[i:i + 64], *w)[0] for i in range(0, len(flat), 64)])
+            if sg == "max":
+                return pool_mean_max(flat, sg)
+            # (this route's launches as tests/model_routes_expected.json pins them: a set's projected bags as a list -- table staged, not
+            # derived by four torch launches -- and torch.cat over one chunk too, a copy; dropping either takes a recording of its own)
+            return pool_mean_max(list(flat) if isinstance(flat, VF.ProjectedBags) else flat, sg, join=torch.cat)
+        s = self._pool_spec()
+        if s.widths_fused and s.drop_p == 0 and VF.uniform_bags(flat):        # no mask is drawn: the two rates need not agree
+            return torch.cat([self._scores().pool_bags(chunk, *s.weights)[0] for chunk in VF.bag_chunks(flat)])
         return torch.stack([VF.scored_pool(x, self._attention_scores(x)) for x in flat])
+
+    def _pool_spec(self) -> _PoolSpec:
+        """the pooling module's parts, per call (plain dict look-ups: seven nn.Sequential.__getitem__ calls are 10 us of a 40 us module call)"""
+        sg = self._modules["sigma"]
+        sm = sg._modules
+        if isinstance(sg, Gated_Attention_Pooling):
+            f1, sc = sm["fc1"]._modules, sm["score"]._modules
+            lin_a, lin_g, lin_o, p_a, p_g = f1["0"], sc["0"], sm["fc2"], f1["2"].p, sc["2"].p
+            weights = (lin_a.weight, lin_a.bias, lin_g.weight, lin_g.bias, lin_o.weight, lin_o.bias)
+            drop_p = float(p_a) if (sg.training and p_a > 0) else 0.0
+        else:
+            at = sm["attention"]._modules
+            lin_a, lin_g, lin_o, p_a, p_g, drop_p = at["0"], None, at["2"], 0.0, 0.0, 0.0
+            weights = (lin_a.weight, lin_a.bias, None, None, lin_o.weight, lin_o.bias)
+        return _PoolSpec(lin_g is not None, lin_a, lin_g, lin_o, weights, drop_p, p_a == p_g,
+                         lin_a.in_features == 512 and lin_a.out_features == 256)
+
+    def _scores(self):
+        """the fused score kernels' host object (packed weights, scratch), made on first use"""
+        fs = self.__dict__.get("_fused_scores")
+        if fs is None:
+            fs = self._fused_scores = VF.FusedAttnScores()
+        return fs
+
+    def head(self, f):
+        """[B, C] pooled bag vectors -> what the encoder returns (model/deepmil.py:283-288): the Adapter mixed in with ``keep_ratio``, or ``g``"""
+        if self.pred_head == "Adapter":
+            return self.keep_ratio * f + (1 - self.keep_ratio) * self.visual_adapter(f)
+        return self.g(f)
 
     def _attention_scores(self, X2):
         """raw scores a[N] of the pooling module on all patches.  512 -> 256 hidden (the reference's sizes): ONE fused MFMA kernel,
         hidden activations in registers -- inference, and under autograd as well (HIP backward that recomputes them tile by tile,
         vlsa_attn_scores_backward), the gated module's training-mode dropout included (counter-based masks inside both kernels).
         Other widths, or a bag that itself carries a gradient: library GEMMs for the hidden projections + torch / HIP elementwise."""
-        sg = self.sigma
-        gated = isinstance(sg, Gated_Attention_Pooling)
-        lin_a = sg.fc1[0] if gated else sg.attention[0]
+        sg = self._modules["sigma"]
+        s = self._pool_spec()
+        lin_a, drop_p = s.lin_a, s.drop_p
         grad_mode = torch.is_grad_enabled()
         bag_grad = grad_mode and X2.requires_grad
         need_grad = bag_grad or (grad_mode and any(p.requires_grad for p in sg.parameters()))
-        drop_p = float(sg.fc1[2].p) if (gated and sg.training and sg.fc1[2].p > 0) else 0.0
-        if (not bag_grad and (not gated or sg.fc1[2].p == sg.score[2].p)
-                and VF.FusedAttnScores.supported(X2, lin_a.in_features, lin_a.out_features)):
-            if not hasattr(self, "_fused_scores"):
-                self._fused_scores = VF.FusedAttnScores()
-            w = ((lin_a.weight, lin_a.bias, sg.score[0].weight, sg.score[0].bias, sg.fc2.weight, sg.fc2.bias) if gated else
-                 (lin_a.weight, lin_a.bias, None, None, sg.attention[2].weight, sg.attention[2].bias))
+        if not bag_grad and s.rates_equal and s.widths_fused and _device_bag(X2):
             if need_grad or drop_p > 0:
-                return VF.attn_scores_autograd(X2, self._fused_scores, *w, drop_p=drop_p)
-            return self._fused_scores(X2, *w)
+                return VF.attn_scores_autograd(X2, self._scores(), *s.weights, drop_p=drop_p)
+            return self._scores()(X2, *s.weights)
         VF.nat.note_torch_route("DeepMIL attention scores", X2.shape[0],
                                 f"widths {lin_a.in_features} -> {lin_a.out_features}, bag gradient {bag_grad}: the fused score kernel covers 512 -> 256 "
                                 "hidden units, bags without a gradient of their own and equal dropout rates in both branches")
@@ -422,25 +462,6 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             e = sg.fc1[2](torch.tanh(H + la.bias)) * sg.score[2](torch.sigmoid(Hg + lg.bias))
             return (e @ l2.weight.t() + l2.bias).squeeze(-1)
         return VF.attn_scores(H, Hg, la.bias, lg.bias, l2.weight, l2.bias)
-
-    def _dropout_seed_word(self, device) -> torch.Tensor:
-        """The seed of one batched training forward as a device word: a per-module device counter, its base drawn ONCE from torch's CPU
-        generator (``torch.manual_seed`` governs it), advanced in-stream by every call -- eagerly and in a captured graph's replays
-        alike -- and snapshotted, so that the backward of this call reads the seed its forward read."""
-        ctr = self.__dict__.get("_drop_counter")
-        if ctr is None or ctr.device != device:
-            base = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            ctr = self._drop_counter = torch.full((1,), base, dtype=torch.int64, device=device)
-        ctr.add_(1)
-        return ctr.clone()
-
-    def _pool_modules(self):
-        sm = self.sigma._modules
-        if isinstance(self.sigma, Gated_Attention_Pooling):
-            f1, sc = sm["fc1"]._modules, sm["score"]._modules
-            return f1["0"], sc["0"], sm["fc2"], f1["2"], sc["2"]
-        at = sm["attention"]._modules
-        return at["0"], None, at["2"], None, None
 
     def forward_bags(self, bags, ret_with_attn=False, projected=False):
         """A list of bags (each [1, N_i, C] or [N_i, C]; a ``BagSet`` is taken as checked) through this encoder as a batch:
@@ -464,38 +485,22 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             flat = self.feat_proj.forward_bags(flat)          # fp32 [N, 512]; a trainable projecter gets dX from the pooling
         if len(flat) == 0:
             raise ValueError("forward_bags needs at least one bag")
-        bag_grad = torch.is_grad_enabled() and any(x.requires_grad for x in flat)
-        uniform = _batch_pools(flat)
         attn = None
         if f is not None:
             pass
-        elif sg == "mean":
-            if uniform:
-                f = _pool_chunks(flat, VF.mean_pool_bags)     # with a bag gradient: one node per chunk, dX of all bags in one launch
-            else:
-                f = torch.stack([x.float().mean(dim=0) if (bag_grad or not x.is_cuda) else VF.scored_pool(x, None) for x in flat])
-        elif sg == "max":
-            if uniform and (bag_grad or len(flat) > 1):
-                f = _pool_chunks(flat, VF.max_pool_bags)
-            else:                                             # one bag per call without a gradient: the single-bag launch pair
-                f = torch.stack([x.float().amax(dim=0) if (bag_grad or not x.is_cuda) else VF.colmax(x) for x in flat])
+        elif isinstance(sg, str):
+            f = pool_mean_max(flat, sg, bag_grad=torch.is_grad_enabled() and any(x.requires_grad for x in flat))
         else:
-            gated = isinstance(sg, Gated_Attention_Pooling)
-            lin_a, lin_g, lin_o, drop_a, drop_g = self._pool_modules()
-            if not (uniform and (not gated or drop_a.p == drop_g.p) and lin_a.in_features == 512 and lin_a.out_features == 256):
+            s = self._pool_spec()
+            if not (s.widths_fused and s.rates_equal and VF.uniform_bags(flat)):     # (the kernels draw both branches' masks at ONE rate)
                 outs = [self.forward(x[None], ret_with_attn=ret_with_attn, _projected=True) for x in flat]     # other widths: per bag
                 if ret_with_attn:
                     return torch.cat([o[0] for o in outs]), [o[1] for o in outs]
                 return torch.cat(outs)
-            if not hasattr(self, "_fused_scores"):
-                self._fused_scores = VF.FusedAttnScores()
-            w = (lin_a.weight, lin_a.bias, lin_g.weight if gated else None, lin_g.bias if gated else None, lin_o.weight, lin_o.bias)
-            drop_p = float(drop_a.p) if (gated and sg.training and drop_a.p > 0) else 0.0
             feats, scores = [], []
-            for i in range(0, len(flat), 64):
-                chunk = flat.chunk(i, 64) if isinstance(flat, VF.BagSet) else (flat if len(flat) <= 64 else flat[i:i + 64])
-                seed = self._dropout_seed_word(chunk[0].device) if drop_p else None
-                pooled, a = VF.attn_pool_bags_autograd(chunk, self._fused_scores, *w, drop_p=drop_p, seed_word=seed)
+            for chunk in VF.bag_chunks(flat):
+                seed = self._dropout_seed_word(chunk[0].device) if s.drop_p else None
+                pooled, a = VF.attn_pool_bags_autograd(chunk, self._scores(), *s.weights, drop_p=s.drop_p, seed_word=seed)
                 feats.append(pooled)
                 if ret_with_attn:
                     o = 0
@@ -503,13 +508,10 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
                         n = x.shape[0]
                         scores.append(a[o:o + n])
                         o += n
-            f = feats[0] if len(feats) == 1 else torch.cat(feats)
+            f = VF.cat(feats)
             if ret_with_attn:
-                attn = [(s[None, :] if not gated else F.softmax(s, dim=0)[None, :]).detach() for s in scores]
-        if self.pred_head == "Adapter":
-            logit = self.keep_ratio * f + (1 - self.keep_ratio) * self.visual_adapter(f)
-        else:
-            logit = self.g(f)
+                attn = [(a[None, :] if not s.gated else F.softmax(a, dim=0)[None, :]).detach() for a in scores]
+        logit = self.head(f)
         if ret_with_attn:
             if attn is None:
                 raise NotImplementedError("ret_with_attn: mean / max pooling has no attention (model/deepmil.py:270-283)")
@@ -522,46 +524,31 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
             X = self.feat_proj(X)
         raw_attn = fused_logit = None
         x_grad = torch.is_grad_enabled() and X.requires_grad   # a trainable Feat_Projecter in front: the pooling must hand dX back
-        if self.sigma == "mean":
+        module = self._modules.get("sigma")     # (one dict read; None: 'mean' / 'max', a plain attribute)
+        if module is None and self.sigma == "mean":
             out_feat = X.float().mean(dim=1) if x_grad else VF.scored_pool(X, None)[None, :]
-        elif self.sigma == "max":
+        elif module is None:
             out_feat = X.float().amax(dim=1) if x_grad else VF.colmax(X)[None, :]
         else:
             X2 = VF._bag2d(X)
-            sg = self.sigma
-            gated = isinstance(sg, Gated_Attention_Pooling)
-            sm = sg._modules          # (plain dict look-ups: seven nn.Sequential.__getitem__ calls are 10 us of a 40 us module call)
-            if gated:
-                f1, sc = sm["fc1"]._modules, sm["score"]._modules
-                lin_a, lin_g, lin_o, drop_a, drop_g = f1["0"], sc["0"], sm["fc2"], f1["2"], sc["2"]
-            else:
-                at = sm["attention"]._modules
-                lin_a, lin_g, lin_o, drop_a, drop_g = at["0"], None, at["2"], None, None
-            if (x_grad and (not gated or drop_a.p == drop_g.p)
-                    and VF.FusedAttnScores.supported(X2, lin_a.in_features, lin_a.out_features)):
+            s = self._pool_spec()
+            fits = s.widths_fused and _device_bag(X2)
+            if x_grad and fits and s.rates_equal:
                 # scores + pooling as ONE autograd node whose backward is HIP end to end: parameter gradients AND
                 # dX = dHa Wa + dHg Wg + A dpooled (vlsa_attn_scores_backward_dx); 512 -> 256 hidden, the reference's sizes
-                if not hasattr(self, "_fused_scores"):
-                    self._fused_scores = VF.FusedAttnScores()
-                w = (lin_a.weight, lin_a.bias, lin_g.weight if gated else None, lin_g.bias if gated else None, lin_o.weight, lin_o.bias)
-                drop_p = float(drop_a.p) if (gated and sg.training and drop_a.p > 0) else 0.0
-                pooled, a = VF.attn_pool_autograd(X2, self._fused_scores, *w, drop_p=drop_p)
+                pooled, a = VF.attn_pool_autograd(X2, self._scores(), *s.weights, drop_p=s.drop_p)
                 out_feat = pooled[None, :]
             else:
                 fused = None
-                if (not torch.is_grad_enabled() and not (gated and sg.training and drop_a.p > 0)
-                        and VF.FusedAttnScores.supported(X2, lin_a.in_features, lin_a.out_features)):
+                if not torch.is_grad_enabled() and fits and s.drop_p == 0:       # no mask is drawn: the two rates need not agree
                     # inference on a large bf16 bag: scores and pooling in ONE launch (vlsa_gated_scores_pool / _adapter)
-                    if not hasattr(self, "_fused_scores"):
-                        self._fused_scores = VF.FusedAttnScores()
-                    w = (lin_a.weight, lin_a.bias, lin_g.weight if gated else None, lin_g.bias if gated else None, lin_o.weight, lin_o.bias)
                     adapter = None
                     if self.pred_head == "Adapter":
                         fc = self.visual_adapter._modules["fc"]._modules
                         W1, W2 = fc["0"].weight, fc["2"].weight
                         if W1.shape[1] == 512 and W2.shape[0] == 512 and W1.shape[0] % 4 == 0:
                             adapter = (W1, W2, self.keep_ratio)
-                    fused = self._fused_scores.scores_and_pool(X2, *w, adapter=adapter)
+                    fused = self._scores().scores_and_pool(X2, *s.weights, adapter=adapter)
                 if fused is not None:
                     out_feat, a = fused[0], fused[1]
                     if len(fused) == 3:
@@ -573,17 +560,15 @@ class DeepMIL(VF.nat.TransientCaches, nn.Module):
                     else:
                         out_feat = VF.scored_pool(X2, a)[None, :]
             if ret_with_attn:  # what the reference hands back: raw scores (attention) / softmax weights (gated attention)
-                raw_attn = a[None, :] if isinstance(self.sigma, Attention_Pooling) else F.softmax(a, dim=0)[None, :]
+                raw_attn = a[None, :] if not s.gated else F.softmax(a, dim=0)[None, :]
         if fused_logit is not None:
             logit = fused_logit                      # (computed behind the pooling in the same host call)
-        elif self.pred_head == "Adapter":
+        elif (self.pred_head == "Adapter" and out_feat.is_cuda
+              and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.visual_adapter.fc.parameters()))):
             fc = self.visual_adapter.fc
-            if not (torch.is_grad_enabled() and any(p.requires_grad for p in fc.parameters())) and out_feat.is_cuda:
-                logit = VF.adapter_head(out_feat, fc[0].weight, fc[2].weight, self.keep_ratio)[None, :]   # two small HIP launches
-            else:
-                logit = self.keep_ratio * out_feat + (1 - self.keep_ratio) * self.visual_adapter(out_feat)
+            logit = VF.adapter_head(out_feat, fc[0].weight, fc[2].weight, self.keep_ratio)[None, :]   # two small HIP launches
         else:
-            logit = self.g(out_feat)
+            logit = self.head(out_feat)
         if ret_with_attn:
             return logit, raw_attn.detach()
         return logit
@@ -607,7 +592,7 @@ class _BClassifier(nn.Module):
         self.fcc = nn.Conv1d(output_class, output_class, kernel_size=hid_size)
 
 
-class DSMIL(VF.nat.TransientCaches, nn.Module):
+class DSMIL(VF.nat.TransientCaches, _DropoutSeed, nn.Module):
     """DSMIL (Li et al., CVPR 2021; model/deepmil.py:692-721) with the reference's constructor and state-dict keys
     (``i_classifier.fc.0.*``, ``b_classifier.q.*``, ``b_classifier.v.1.*``, ``b_classifier.fcc.*``, ``feat_proj.*``).
 
@@ -625,8 +610,6 @@ class DSMIL(VF.nat.TransientCaches, nn.Module):
         self.i_classifier = _FCLayer(in_size=dim_in, out_size=num_cls)
         self.b_classifier = _BClassifier(dim_in, dim_hid, num_cls, dropout_v=drop_rate)
 
-    _dropout_seed_word = DeepMIL._dropout_seed_word
-
     def _weights(self):
         bc = self.b_classifier._modules
         fc = self.i_classifier._modules["fc"]._modules["0"]
@@ -641,27 +624,24 @@ class DSMIL(VF.nat.TransientCaches, nn.Module):
         if Wc.shape[1] != 512 or Wq.shape[0] != 256 or not (1 <= Wc.shape[0] <= 16):
             raise VF.VlsaNativeError(f"DSMIL: the HIP kernels cover dim_in = 512, dim_hid = 256, num_cls <= 16 (got {Wc.shape[1]}, "
                                      f"{Wq.shape[0]}, {Wc.shape[0]}); there is no other route")
-        grad = torch.is_grad_enabled()
-        is_set = isinstance(bags, VF.BagSet)
-        if not is_set:
-            if len(bags) == 0:
-                raise ValueError("forward_bags needs at least one bag")
-            VF._need_gpu(*bags)
-            bags = [VF._bag2d(x) for x in bags]
+        grad, is_set = torch.is_grad_enabled(), isinstance(bags, VF.BagSet)
+        if not is_set and len(bags) == 0:
+            raise ValueError("forward_bags needs at least one bag")
+        VF._need_gpu(*(() if is_set else bags))
+        # (the three refusals in the order they always had: a bag's gradient, the projecter's, then the bags' shapes)
         if grad and any(x.requires_grad for x in bags):
             raise VF.VlsaNativeError("DSMIL: the bag requires grad, but the HIP backward produces parameter gradients only (no dX)")
         if self.feat_proj is not None and not projected:
             if grad and any(p.requires_grad for p in self.feat_proj.parameters()):
                 raise VF.VlsaNativeError("DSMIL: a trainable Feat_Projecter needs the gradient of the bag rows, which the DSMIL backward does "
                                          "not produce; freeze feat_proj (requires_grad_(False)) or run under torch.no_grad()")
-        if not is_set and not all(x.shape[1] == 512 and x.shape[0] > 0 and x.dtype == bags[0].dtype and x.device == bags[0].device
-                                  for x in bags):
-            raise VF.VlsaNativeError("DSMIL takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device")
+        if not is_set:
+            bags = VF.checked_bags(bags, 512, "DSMIL takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device",
+                                   non_empty=True)
         drop = self.b_classifier._modules["v"]._modules["0"]
         drop_p = float(drop.p) if (self.training and drop.p > 0) else 0.0
         logits, attn, crit = [], [], []
-        for i in range(0, len(bags), 64):
-            chunk = bags.chunk(i, 64) if is_set else (bags if len(bags) <= 64 else bags[i:i + 64])
+        for chunk in VF.bag_chunks(bags):
             if self.feat_proj is not None and not projected:
                 chunk = self.feat_proj.forward_bags(chunk)
                 if not isinstance(chunk, VF.ProjectedBags):
@@ -672,11 +652,11 @@ class DSMIL(VF.nat.TransientCaches, nn.Module):
             crit.append(cr)
             if ret_with_attn:
                 attn.extend(t[None, :] for t in a.split([int(x.shape[0]) for x in chunk]))
-        out = (logits[0] if len(logits) == 1 else torch.cat(logits),)
+        out = (VF.cat(logits),)
         if ret_with_attn:
             out += (attn,)
         if ret_critical:
-            out += (crit[0] if len(crit) == 1 else torch.cat(crit),)
+            out += (VF.cat(crit),)
         return out[0] if len(out) == 1 else out
 
     def forward(self, X, **kwargs):
@@ -728,11 +708,9 @@ class DeepAttnMISL(nn.Module):
                                      f"{Wp.shape[1]}, {Wp.shape[0]}, {Kc}); there is no other route")
         if len(bags) == 0 or len(bags) != len(cluster_ids):
             raise ValueError("forward_bags needs at least one bag and one cluster-id tensor per bag")
-        out = [VF.cluster_pool_bags(bags[i:i + 64], cluster_ids[i:i + 64], Wp, bp, num_clusters=Kc, ret_state=ret_state)
-               for i in range(0, len(bags), 64)]
-        if not ret_state:
-            return out[0] if len(out) == 1 else torch.cat(out)
-        return tuple(o[0] if len(out) == 1 else torch.cat(o) for o in zip(*out))
+        out = [VF.cluster_pool_bags(chunk, ids, Wp, bp, num_clusters=Kc, ret_state=ret_state)
+               for chunk, ids in zip(VF.bag_chunks(bags), VF.bag_chunks(cluster_ids))]
+        return tuple(VF.cat(o) for o in zip(*out)) if ret_state else VF.cat(out)
 
     def forward_bags(self, bags, cluster_ids, ret_state=False):
         """logits [B, num_cls] of a list of bags and their cluster ids: ``torch.cat([self(x, c) for x, c in zip(bags, cluster_ids)])``"""
@@ -898,29 +876,16 @@ class ILRA(nn.Module):
         self._check_served()
         if len(bags) == 0:
             raise ValueError("forward_bags needs at least one bag")
-        if isinstance(bags, VF.BagSet):
-            sizes = bags.sizes
-        else:
+        if not isinstance(bags, VF.BagSet):
             bags = VF.checked_bags(bags, 512, "ILRA takes non-empty bags with 512 features, one dtype (bf16 or fp32) and one device",
                                    non_empty=True, no_grad="ILRA: the bag requires grad, but bag rows receive no gradient from the HIP kernels")
-            sizes = [int(x.shape[0]) for x in bags]
         VF._need_gpu(self.classifier.weight)
         with torch.autocast(device_type="cuda", enabled=False):
             prep = [self._queries(blk.project_forward, blk.latent) for blk in self.gab_blocks]
             prep.append(self._queries(self.pooling.mha, self.pooling.S))
-            outs, states, i = [], [], 0
-            while i < len(sizes):
-                j, rows = i + 1, sizes[i]
-                while j < len(sizes) and j - i < 64 and rows + sizes[j] <= self.ROW_BUDGET:
-                    rows += sizes[j]
-                    j += 1
-                chunk = bags.chunk(i, j - i) if isinstance(bags, VF.BagSet) else bags[i:j]
-                lg, st = self._chunk(chunk, prep, ret_state)
-                outs.append(lg)
-                states.append(st)
-                i = j
-        logits = outs[0] if len(outs) == 1 else torch.cat(outs)
-        return (logits, states) if ret_state else logits
+            outs, states = zip(*[self._chunk(chunk, prep, ret_state) for chunk in VF.bag_chunks(bags, 64, self.ROW_BUDGET)])
+        logits = VF.cat(outs)
+        return (logits, list(states)) if ret_state else logits
 
     def forward(self, X):
         return self.forward_bags([X])

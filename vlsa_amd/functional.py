@@ -17,8 +17,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from ._native import VlsaNativeError
-from .bag_tables import (ChunkTables, _bag2d, _dt, _need_gpu, _p, _stage_table, _stream, bag_rows, checked_bags,  # noqa: F401
-                         merge_strides)
+from .bag_tables import (ChunkTables, _bag2d, _dt, _need_gpu, _p, _stage_table, _stream, bag_chunks, bag_rows, cat,  # noqa: F401
+                         checked_bags, merge_strides, uniform_bags)
 
 COATTN_SCALE = 100.0  # exp(coattn_logit_scale), model/deepmil.py:120-126
 

@@ -10,6 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._native import TransientCaches as _TransientCaches
+from .bag_tables import bag_chunks, cat, is_bag_set, uniform_bags
 
 
 class Adapter(nn.Module):
@@ -61,19 +62,13 @@ class Feat_Projecter(_TransientCaches, nn.Module):
         return self.projecter(x)
 
     def serves_batch(self, bags) -> bool:
-        """whether the batch kernel (vlsa_feat_project_batch) takes these bags behind this projecter: device tensors of one dtype
-        (bf16 or fp32) and width 512 without a gradient of their own, no empty bag, Linear(512, 512) + affine LayerNorm(512)"""
-        from . import functional as VF
+        """whether the batch kernel (vlsa_feat_project_batch) takes these bags behind this projecter: ``uniform_bags`` (device tensors
+        of one dtype and width 512, no empty bag) without a gradient of their own (a ``BagSet`` holds none), Linear(512, 512) + affine
+        LayerNorm(512)"""
         lin, norm = self.projecter[0], self.projecter[1]
-        is_set = isinstance(bags, VF.BagSet)
-        grad = torch.is_grad_enabled()
-
-        def takes(x):
-            return (x.is_cuda and (x.dim() == 2 or (x.dim() == 3 and x.shape[0] == 1)) and x.shape[-1] == 512 and x.shape[-2] > 0
-                    and x.dtype == bags[0].dtype and x.device == bags[0].device and not (grad and x.requires_grad))
-        return (len(bags) > 0 and lin.in_features == 512 and lin.out_features == 512 and tuple(norm.normalized_shape) == (512,)
-                and norm.elementwise_affine and lin.weight.is_cuda and bags[0].dtype in (torch.bfloat16, torch.float32)
-                and ((is_set and bags.D == 512) or all(takes(x) for x in bags)))
+        return (lin.in_features == 512 and lin.out_features == 512 and tuple(norm.normalized_shape) == (512,)
+                and norm.elementwise_affine and lin.weight.is_cuda and uniform_bags(bags)
+                and not (torch.is_grad_enabled() and not is_bag_set(bags) and any(x.requires_grad for x in bags)))
 
     def forward_bags(self, bags):
         """``[self(x) for x in bags]`` for a list (or ``BagSet``) of bags, each [N_i, 512] or [1, N_i, 512]: ONE fused HIP launch per
@@ -83,7 +78,7 @@ class Feat_Projecter(_TransientCaches, nn.Module):
         itself requires grad, mixed dtypes, an empty bag -- goes bag by bag through ``forward``."""
         from . import functional as VF
         lin, norm = self.projecter[0], self.projecter[1]
-        is_set = isinstance(bags, VF.BagSet)
+        is_set = is_bag_set(bags)
         if not self.serves_batch(bags):
             return [self.forward(x) for x in bags]
         if not hasattr(self, "_fused"):
@@ -91,11 +86,10 @@ class Feat_Projecter(_TransientCaches, nn.Module):
         if is_set and len(bags) <= 64:          # one chunk of a BagSet: the packed views with their device-side table, as they are
             return self._fused.forward_bags(bags, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps)
         out = []
-        for i in range(0, len(bags), 64):
-            chunk = bags.chunk(i, 64) if is_set else [VF._bag2d(x) for x in bags[i:i + 64]]
-            out.extend(self._fused.forward_bags(chunk, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps))
+        for chunk in bag_chunks(bags):
+            out.extend(self._fused.forward_bags(chunk if is_set else [VF._bag2d(x) for x in chunk], lin.weight, lin.bias, norm.weight, norm.bias,
+                                                norm.eps))
         return out if is_set else [y if x.dim() == 2 else y[None] for x, y in zip(bags, out)]
-
 
     def trains(self) -> bool:
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -108,12 +102,9 @@ class Feat_Projecter(_TransientCaches, nn.Module):
         lin, norm = self.projecter[0], self.projecter[1]
         if not hasattr(self, "_fused"):
             self._fused = VF.FusedFeatProjecter()
-        is_set = isinstance(bags, VF.BagSet)
-        out = []
-        for i in range(0, len(bags), 64):
-            chunk = bags.chunk(i, 64) if is_set else [VF._bag2d(x) for x in bags[i:i + 64]]
-            out.append(VF.project_max_pool_bags(chunk, self._fused, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps))
-        return out[0] if len(out) == 1 else torch.cat(out)
+        is_set = is_bag_set(bags)
+        return cat([VF.project_max_pool_bags(chunk if is_set else [VF._bag2d(x) for x in chunk], self._fused, lin.weight, lin.bias, norm.weight,
+                                             norm.bias, norm.eps) for chunk in bag_chunks(bags)])
 
 
 def _note(module, x):

@@ -72,11 +72,6 @@ def build_mil_encoder(image_encoder_cfg: dict) -> nn.Module:
     return cls(**image_encoder_cfg)
 
 
-def _device_bags_512(bags) -> bool:
-    """a non-empty list of device bags [..., N > 0, 512] of one dtype: what the batched HIP routes take"""
-    return len(bags) > 0 and all(x.is_cuda and x.dtype == bags[0].dtype and x.shape[-1] == 512 and x.shape[-2] > 0 for x in bags)
-
-
 def _encoder_extras(model):
     """the encoder watch's extras (a function of the model: no reference back to it): logit scale, plain-attribute co-attention scale"""
     cs = getattr(model._modules["mil_encoder"], "coattn_logit_scale", None)
@@ -841,7 +836,9 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return self._forward_bags_attn(bags, text_features)
         if self._needs_grad(text_features):
             self._invalidate(_FORWARD)           # a differentiable forward: parameters are about to move (see _lookahead)
-            if isinstance(enc, VLFAN) and _device_bags_512(bags):
+            # (this site's own, looser condition, not ``uniform_bags``: the route behind it converts other dtypes through _bag2d)
+            if (isinstance(enc, VLFAN) and len(bags) > 0
+                    and all(x.is_cuda and x.dtype == bags[0].dtype and x.shape[-1] == 512 and x.shape[-2] > 0 for x in bags)):
                 spec = enc.fused_head_spec()
                 if (spec is not None and spec[0] == "mean" and text_features.is_cuda and text_features.shape[0] <= 64
                         and text_features.shape[1] == 512):
@@ -875,15 +872,13 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             return None
         bagset = bags if isinstance(bags, VF.BagSet) and bags.D == 512 else None
         flat = bagset if bagset is not None else [VF._bag2d(x) for x in bags]
-        if bagset is None and not all(x.is_cuda and x.dtype == flat[0].dtype and x.dtype in (torch.bfloat16, torch.float32)
-                                      and x.shape[1] == 512 and x.shape[0] > 0 and not x.requires_grad for x in flat):
+        if not VF.uniform_bags(flat) or (bagset is None and any(x.requires_grad for x in flat)):
             return None
         k = _parse_logit_pooling(self.image_encoder_cfg["pooling"])
         if k is not None and not (1 <= k <= 32):
             return None
-        outs = [VF.zeroshot_pool_bags(bagset.chunk(i, 64) if bagset is not None else flat[i:i + 64], T, ls, k, return_text=True)
-                for i in range(0, len(flat), 64)]
-        logits = outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs])
+        outs = [VF.zeroshot_pool_bags(chunk, T, ls, k, return_text=True) for chunk in VF.bag_chunks(flat)]
+        logits = VF.cat([o[0] for o in outs])
         feats = [VF.normalize_many(x) for x in flat] if getattr(self, "return_patch_features", None) is True else None
         return logits, feats, outs[0][1]
 
@@ -913,7 +908,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         grad = self._needs_grad(text_features)
         spec = enc.fused_head_spec()
         flat = [VF._bag2d(x) for x in bags]
-        if grad or spec is None or spec[0] == "module" or not _device_bags_512(flat):
+        if grad or spec is None or spec[0] == "module" or not VF.uniform_bags(flat):
             with torch.set_grad_enabled(grad):
                 text_n = F.normalize(text_features, dim=-1)
                 feats, attn = enc.forward_bags(bags, ret_with_attn=True)
@@ -938,27 +933,21 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
             flat = enc.feat_proj.forward_bags(flat)    # use_feat_proj=True: one fused HIP launch per 64 bags, fp32 [N, 512] out
             projected = True
         ok = (spec is not None and spec[0] != "module" and len(flat) > 0
-              and ((trusted and not projected) or _device_bags_512(flat)))
+              and ((trusted and not projected) or VF.uniform_bags(flat)))
         if not ok:
-            same = _device_bags_512(flat) and flat[0].dtype in (torch.bfloat16, torch.float32)
+            same = VF.uniform_bags(flat)
             if same and isinstance(enc, FeatMIL) and enc.pooling not in ("mean", "max") and text_features.shape[0] <= 64:
                 return self._forward_bags_zeroshot(flat, text_features)
             if same and isinstance(enc, FeatMIL) and enc.pooling in ("mean", "max"):
                 # FeatMIL baseline (model/deepmil.py:57-60): row means / column maxima of all bags in two launches per 64 bags
-                # (one bag per call: the single-bag launch pair), then normalise + cosine logits on [B, 512]
-                if enc.pooling == "mean":
-                    f = torch.cat([VF.mean_pool_bags(flat[i:i + 64]) for i in range(0, len(flat), 64)])
-                elif len(flat) > 1:
-                    f = torch.cat([VF.max_pool_bags(bagset.chunk(i, 64) if bagset is not None else flat[i:i + 64])
-                                   for i in range(0, len(flat), 64)])
-                else:
-                    f = torch.stack([VF.colmax(x) for x in flat])
+                # (one bag per call: the single-bag launch pair; torch.cat over one chunk too, as the route recording pins), then normalise + logits
+                f = mil_encoders.pool_mean_max(flat, enc.pooling, join=torch.cat)
                 That = F.normalize(text_features.detach().float(), dim=-1)
                 feats = F.normalize(f, dim=-1)
                 return self.logit_scale.exp() * feats @ That.t(), feats, That
             if same and isinstance(enc, mil_encoders.DeepMIL) and (enc.feat_proj is None or projected):
                 return self._forward_bags_deepmil(flat, text_features)
-            if isinstance(enc, VLFAN) and (enc.feat_proj is None or projected) and _device_bags_512(flat):
+            if isinstance(enc, VLFAN) and (enc.feat_proj is None or projected) and same:
                 # pooling over the queries by a module (attention / gated attention): batched HIP aggregation, then the
                 # module, the adapter and the cosine logits as batched torch ops on [B, P, 512]
                 That = F.normalize(text_features, dim=-1)
@@ -1031,7 +1020,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         from .deepmil import _parse_logit_pooling
         k = _parse_logit_pooling(self.image_encoder_cfg["pooling"])
         T = text_features.detach().float().contiguous()
-        logits = torch.cat([VF.zeroshot_pool_bags(flat[i:i + 64], T, self.logit_scale.detach(), k) for i in range(0, len(flat), 64)])
+        logits = torch.cat([VF.zeroshot_pool_bags(chunk, T, self.logit_scale.detach(), k) for chunk in VF.bag_chunks(flat)])
         That, _ = VF.normalize_rows(T)
         feats = [VF.normalize_many(x) for x in flat] if getattr(self, "return_patch_features", None) is True else None
         return logits, feats, That
@@ -1041,11 +1030,7 @@ class VLSA(VF.nat.TransientCaches, nn.Module):
         launch and one pooling launch per <= 64 bags (``DeepMIL.pool_bags``), then ONE batched tail for all bags (head,
         normalise, cosine logits on [B, 512])."""
         enc = self.mil_encoder
-        f = enc.pool_bags(flat)                                                      # [B, 512]
-        if enc.pred_head == "Adapter":
-            v = enc.keep_ratio * f + (1 - enc.keep_ratio) * enc.visual_adapter(f)
-        else:
-            v = enc.g(f)
+        v = enc.head(enc.pool_bags(flat))                                            # [B, 512]
         That = F.normalize(text_features.detach().float(), dim=-1)
         feats = F.normalize(v, dim=-1)
         return self.logit_scale.exp() * feats @ That.t(), feats, That
