@@ -53,16 +53,33 @@ def pair_counts(time, event, est, tied_tol=1e-8):
     return n_con, n_comp - n_con - n_tied, n_tied, int(same.sum()), n_comp
 
 
+def pair_counts_blocked(time, event, est, tied_tol=1e-8, rows=512):
+    """pair_counts, `rows` samples i at a time: the all-pairs matrices of M = 16 385 would take 2 GB"""
+    time, est = np.asarray(time, dtype=np.float64), np.asarray(est, dtype=np.float64)
+    event = np.asarray(event) != 0
+    n_comp = n_con = n_tied = n_same = 0
+    for i0 in range(0, len(time), rows):
+        ev = event[i0:i0 + rows, None]
+        ti, si = time[i0:i0 + rows, None], est[i0:i0 + rows, None]
+        same = ev & (time[None, :] == ti) & ~event[None, :]
+        comp = (ev & (time[None, :] > ti)) | same
+        tied = np.abs(est[None, :] - si) <= tied_tol
+        n_con += int((comp & ~tied & (est[None, :] < si)).sum())
+        n_comp, n_tied, n_same = n_comp + int(comp.sum()), n_tied + int((comp & tied).sum()), n_same + int(same.sum())
+    return n_con, n_comp - n_con - n_tied, n_tied, n_same, n_comp
+
+
 def cindex(counts):
     con, _, tied, _, comp = counts
     return (float(con) + 0.5 * float(tied)) / float(comp)
 
 
-def loss_mle(y_hat, t, e, prediction_type, alpha=0.0, eps=1e-7, reduce=True):
-    y_hat = torch.as_tensor(y_hat).double()
+def loss_mle(y_hat, t, e, prediction_type, alpha=0.0, eps=1e-7, reduce=True, dtype=torch.float64):
+    """dtype: the precision the formulas are evaluated in (float64: the truth; float32: what a plain fp32 evaluation of them reaches)"""
+    y_hat = torch.as_tensor(y_hat).to(dtype)
     M = y_hat.shape[0]
     t = torch.as_tensor(t).view(M, 1).long()
-    c = 1.0 - torch.as_tensor(e).view(M, 1).double()
+    c = 1.0 - torch.as_tensor(e).view(M, 1).to(dtype)
     if prediction_type == "incidence":
         unc = -(1 - c) * torch.log(torch.gather(y_hat, 1, t).clamp(min=eps))
         cen = -c * torch.log((1 - torch.gather(torch.cumsum(y_hat, dim=1), 1, t)).clamp(min=eps))
@@ -89,6 +106,24 @@ def loss_emd(y_hat, t, e, logit_scale, p=2, raw_distance=True):
     if p == 2 and not raw_distance:
         dist = dist.sqrt()
     return float(dist.mean())
+
+
+def loss_emd_rows(y_hat, t, e, logit_scale, p=2, raw_distance=True, dtype=torch.float64):
+    """loss_emd per sample: the [M] tensor whose mean loss_emd returns, differentiable w.r.t. y_hat (dtype: as in loss_mle)"""
+    y_hat = torch.as_tensor(y_hat).to(dtype)
+    M, K = y_hat.shape
+    ls = float(logit_scale)
+    t = torch.as_tensor(t).view(M, 1).long()
+    ei = torch.as_tensor(e).view(M, 1).long()
+    k = torch.arange(K).view(1, K)
+    target = ((k == t).long() + (k > t).long() * (1 - ei)).to(dtype)                # convert_survival_label
+    target_dist = torch.softmax((2 * target - 1) * ls, dim=-1)
+    pred = (1 - ei) * ((1 - target) * y_hat + target * ls) + ei * y_hat
+    d = torch.cumsum(torch.softmax(pred, dim=-1), dim=-1) - torch.cumsum(target_dist, dim=-1)
+    dist = d.abs().sum(dim=-1) if p == 1 else (d ** 2).sum(dim=-1)
+    if p == 2 and not raw_distance:
+        dist = dist.sqrt()
+    return dist
 
 
 def evaluate(raw, t, e, prediction_type, alpha=0.0, eps=1e-7, tied_tol=1e-8, ext=None):
