@@ -16,10 +16,15 @@ TOWERS = {
     "small": dict(width=128, heads=2, layers=2, vocab=VOCAB, ctx=CTX, out_dim=64),
     "w512x2": dict(width=512, heads=8, layers=2, vocab=VOCAB, ctx=CTX, out_dim=512),    # the ViT-B text tower at a sixth of the weights
     "w128x3": dict(width=128, heads=2, layers=3, vocab=VOCAB, ctx=CTX, out_dim=64),     # a block that is neither first nor last
+    # width 768 / 12 heads: the products' static-G shapes (tests/clip_shape_cases.py)
+    "w768x2": dict(width=768, heads=12, layers=2, vocab=VOCAB, ctx=CTX, out_dim=512),
+    "w768x3": dict(width=768, heads=12, layers=3, vocab=VOCAB, ctx=CTX, out_dim=512),
+    "w768x2_o768": dict(width=768, heads=12, layers=2, vocab=VOCAB, ctx=CTX, out_dim=768),   # the ViT-L/14 text side's projection
 }
 # as text_cases.WEIGHT_SCALES: in_proj / c_fc weights rescaled after the draw, so that the attention logits and the QuickGELU inputs
 # leave the range of a freshly initialised tower (|x| past 6: the sigmoid's tails).  seed -> (in_proj factor, c_fc factor)
-WEIGHT_SCALES = {9121: (3.5, 3.5)}
+WEIGHT_SCALES = {9121: (3.5, 3.5),
+                 9141: (3.5, 3.5), 9142: (3.5, 3.5), 9143: (3.5, 3.5)}     # the 768-wide towers of tests/clip_shape_cases.py
 
 
 def make_clip_weights(name: str, seed: int):

@@ -9,16 +9,13 @@ prompt's gradient is ~10x a 62-token prompt's and would hide its error), per ten
 (``1e-4 * max + 1e-7`` there, the rule of test_gpu_text_tower.py).  Yardstick: the fp32 CPU oracle's own distance from the float64 one on
 these inputs, which sets each case's seed without looking at the GPU (tests/text_shape_cases.py ``SEED_STEP``) and which
 tests/test_text_shape_cases_cpu.py holds to <= 2.5e-5, a quarter of the gate, for three of the cases.  Every figure is printed before it is asserted (pytest -s; profiles/r10_pytest_gpu_text_shapes.txt)."""
-import re
-from collections import Counter
-
 import pytest
 import torch
 
 import cases
 import text_cases as TC
 import text_shape_cases as SC
-from text_helpers import tower_kernels
+from text_helpers import count, expected_gemms_768, gemm_names, tower_kernels
 
 pytestmark = pytest.mark.gpu
 GATE = SC.GATE
@@ -106,40 +103,6 @@ def grad_checks(tag, case, got, ref, checks, plus=0.0):
     z = got["d_emb"][behind.cuda()]
     checks.append((f"{tag} exact zeros behind the first pad", torch.equal(z, torch.zeros_like(z))))
     return text
-
-
-def gemm_names(names):
-    """Counter of the k_tt_gemm instantiations among the kernel names: 'MT, NW, PRO, G, NTW' -> launches"""
-    return Counter(m.group(1) for n in names for m in [re.search(r"k_tt_gemm<([^>]*)>", n)] if m)
-
-
-def expected_gemms_768(M, layers, route):
-    """What vlsa_tt_forward + vlsa_tt_backward launch for a frozen tower of width 768 / out_dim 512 (see the table's head comment):
-    template arguments <row tiles, waves, prologue (0 none, 1 LayerNorm, 2 LayerNorm backward), K groups, 16-column tiles>."""
-    w = Counter()
-    tw = 2 if M <= 160 else 3                                                      # the 16-row products' column tiles
-    w["1, 4, 1, 12, 4" if M <= 112 else "2, 4, 1, 12, 3" if M <= 160 else "3, 4, 1, 12, 3"] += layers          # in_proj
-    w["1, 4, 1, 12, 6" if M <= 128 else "2, 4, 1, 12, 4" if M <= 160 else "3, 4, 1, 12, 3"] += layers          # c_fc
-    w[f"1, 4, 0, 12, {tw}"] += layers                                               # out_proj
-    w[f"1, 8, 0, 24, {tw}"] += layers                                               # c_proj
-    w["1, 4, 0, 12, 1"] += 1                                                        # text projection
-    if route is None:
-        return w
-    w["1, 4, 0, 8, 1"] += 1                                                         # d pooled
-    w[f"1, 8, 0, 24, {tw}"] += layers                                               # d ln_2 out = d h_pre W_fc
-    w[f"1, 8, 0, 18, {tw}"] += layers                                               # d ln_1 out = d qkv W_in
-    if route == "fused":
-        w["1, 4, 0, 12, 6"] += 1                                                    # d h_pre, top block
-        w["1, 4, 2, 12, 6"] += layers - 1                                           # ... below it: ln_1 backward of the block above as prologue
-        w["1, 4, 2, 12, 2"] += layers                                               # d attn with ln_2 backward as prologue
-    else:
-        w["1, 4, 0, 12, 6" if M <= 128 else "2, 4, 0, 12, 4" if M <= 160 else "3, 4, 0, 12, 3"] += layers       # d h_pre
-        w[f"1, 4, 0, 12, {tw}"] += layers                                           # d attn
-    return +w
-
-
-def count(names, pattern):
-    return sum(1 for n in names if re.search(pattern, n))
 
 
 @pytest.mark.parametrize("name", [c.name for c in SC.CASES])
