@@ -580,6 +580,54 @@ int vlsa_surv_objective(const float* x, const int64_t* t, const float* e, int B,
                         float* objective, float* grad, void* stream);
 
 /*
+ * The handler's other objectives (runner/vlsa_handler.py:33-41: an incidence family behind the softmax, a hazard family behind the
+ * sigmoid; loss/utils.py:52-76 adds SurvT2I).  The two entries above stay as they are and launch what they always launched.
+ *
+ * vlsa_surv_terms: vlsa_surv_loss with a converter code and the likelihood term named.  family = VLSA_SURV_IFMLE (SurvIFMLE,
+ * loss/loss_surv.py:144-169) or VLSA_SURV_MLE (SurvMLE, loss/loss_surv.py:104-124: S_padded = [1, cumprod(1 - h)],
+ * uncensored = -(1 - c) (log clamp(S_padded[t], eps) + log clamp(h_t, eps)), censored = -c log clamp(S_padded[t + 1], eps));
+ * converter = VLSA_CONV_NONE (x holds incidences / hazards), VLSA_CONV_SOFTMAX or VLSA_CONV_SIGMOID (x holds raw logits,
+ * utils/func.py:43-46; 1 - h is formed as sigmoid(-x)).  Softmax with SurvMLE and sigmoid with SurvIFMLE are VLSA_EUNSUPPORTED, as
+ * the handler refuses them.  SurvEMD (loss/loss_surv_ext.py:43-109) is taken on the converted values of either family.
+ * out_main / out_emd: per-sample losses [B] (either may be NULL); grad [B, K] = d (w_main * main_i + w_emd * emd_i) / d x[i, :]
+ * (NULL to skip).  Any B, K <= VLSA_MAX_K.
+ */
+#define VLSA_CONV_NONE 0
+#define VLSA_CONV_SOFTMAX 1
+#define VLSA_CONV_SIGMOID 2
+#define VLSA_SURV_IFMLE 0
+#define VLSA_SURV_MLE 1
+int vlsa_surv_terms(const float* x, const int64_t* t, const float* e, int B, int K, int converter, int family,
+                    const float* logit_scale_exp, float alpha, float eps, int p, int raw_distance, float w_main, float w_emd,
+                    float* out_main, float* out_emd, float* grad, void* stream);
+/*
+ * vlsa_surv_objective_terms: calc_objective_loss (runner/vlsa_handler.py:241-258) of either family with SurvT2I in ONE launch:
+ * objective[0] = mean_i (w_main * main_i + w_emd * emd_i) + w_t2i * T2I, grad [B, K] = d objective / d x (NULL to skip).  x: raw logits
+ * where w_t2i != 0 (SurvT2I reads them whatever the converter).  T2I (loss/loss_surv_ext.py:145-195): for each bin k a softmax of
+ * x[:, k] over the samples that take part -- the events, and the censored samples with t > k; positives = the events with t == k; a
+ * bin without a positive is skipped.  VLSA_T2I_CL: -mean over the positives of the log-softmax (SupConLoss, lines 111-123);
+ * VLSA_T2I_KL: sum_b td_b (log td_b - log_softmax_b), td = softmax((2 target - 1) logit_scale) (line 186-187; the scale is a constant).
+ * The bins are summed (VLSA_T2I_SUM) or averaged over the counted ones (VLSA_T2I_MEAN); none counted: value and gradient 0.
+ * logit_scale / ls_is_log: as vlsa_surv_objective.  B <= 4096.
+ */
+#define VLSA_T2I_CL 0
+#define VLSA_T2I_KL 1
+#define VLSA_T2I_SUM 0
+#define VLSA_T2I_MEAN 1
+int vlsa_surv_objective_terms(const float* x, const int64_t* t, const float* e, int B, int K, int converter, int family,
+                              const float* logit_scale, int ls_is_log, float alpha, float eps, int p, int raw_distance,
+                              float w_main, float w_emd, float w_t2i, int t2i_loss, int t2i_reduction, float* objective,
+                              float* grad, void* stream);
+/*
+ * vlsa_surv_t2i: SurvT2I alone in two launches (a workgroup per bin, then one pass over the elements): value[0] = weight * T2I,
+ * grad [B, K] = weight * d T2I / d x (either may be NULL, not both).  work: K * VLSA_T2I_WORK_PER_BIN doubles of device scratch.
+ * 1 <= B <= VLSA_EVAL_MAX_M (VLSA_EUNSUPPORTED above).
+ */
+#define VLSA_T2I_WORK_PER_BIN 5
+int vlsa_surv_t2i(const float* x, const int64_t* t, const float* e, int B, int K, const float* logit_scale, int ls_is_log,
+                  int t2i_loss, int t2i_reduction, float weight, double* work, float* value, float* grad, void* stream);
+
+/*
  * Scoring a split on the device: what NLLSurv_Evaluator (eval/evaluator_surv.py:45-235, backend other than SurvivalEVAL) computes on
  * the host from the [M, K] predictions of a pass -- in two launches and one 128-byte result buffer.
  *

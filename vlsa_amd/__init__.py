@@ -5,7 +5,8 @@ in hand-written HIP kernels behind the C ABI of include/vlsa_hip.h.  There is no
 """
 from ._native import VlsaNativeError  # noqa: F401
 
-__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA", "SurvEvaluator", "concordance_index_censored", "concordance_counts"]
+__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA", "SurvEvaluator", "concordance_index_censored", "concordance_counts",
+           "SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective"]
 
 
 def __getattr__(name):
@@ -18,4 +19,7 @@ def __getattr__(name):
     if name in ("SurvEvaluator", "concordance_index_censored", "concordance_counts"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective"):
+        from . import losses
+        return getattr(losses, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -5,6 +5,7 @@
 // One thread per sample; K <= 64 values live in registers / scratch -- the work is a few hundred flops per sample.
 #include "vlsa_common.h"
 #include "launch.h"
+#include "surv_rows16.h"
 
 namespace vlsa {
 
@@ -144,29 +145,7 @@ __global__ __launch_bounds__(kLossThreads) void k_surv_loss(const float* __restr
 // operation through DPP (sum / max by row rotations, the cumulative sums of the EMD term by shifted adds), 32 samples per 512-thread
 // workgroup and pass.  Same formulas; the cumulative sums keep the bin order (see row16_prefix), plain sums run in tree order.  Inside the training
 // step: 12.7 -> 4.7 us = the floor of a launch (the loops above are ~500 dependent LDS accesses on one wave).
-#define VLSA_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true))
-// (row16_sum: vlsa_common.h)
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, VLSA_DPP(v, 0x128)); v = fmaxf(v, VLSA_DPP(v, 0x124)); v = fmaxf(v, VLSA_DPP(v, 0x122)); v = fmaxf(v, VLSA_DPP(v, 0x121));
-    return v;
-}
-// Cumulative sums IN BIN ORDER, as torch.cumsum and its backward add them: c_k = (((v_0 + v_1) + v_2) + ...) + v_k, fifteen dependent
-// shifted adds (after step s lane k holds the left-to-right sum of v_{k-s} .. v_k).  The order matters: the reference clamps
-// 1 - CIF[t] at eps, and whether a censored sample in the last bin lands on the clamp -- zero gradient or c / sv ~ 1e7 -- is decided by the
-// last ulp of that cumsum (a log-step scan moved a 40-step training run off the CPU twin's loss curve by 0.3 % at step 6).
-__device__ __forceinline__ float row16_prefix(float v) {      // inclusive, over the lanes <= this one (row_shr:1, zeros shift in)
-    float c = v;
-#pragma unroll
-    for (int s = 0; s < 15; ++s) c = VLSA_DPP(c, 0x111) + v;
-    return c;
-}
-__device__ __forceinline__ float row16_suffix(float v) {      // inclusive, over the lanes >= this one, added from the right (row_shl:1)
-    float c = v;
-#pragma unroll
-    for (int s = 0; s < 15; ++s) c = VLSA_DPP(c, 0x101) + v;
-    return c;
-}
-#undef VLSA_DPP
+// (row16_sum: vlsa_common.h; row16_max, row16_prefix, row16_suffix: surv_rows16.h)
 constexpr int kLossWide = 512, kLossWideSamples = kLossWide / 16;
 __global__ __launch_bounds__(kLossWide) void k_surv_loss_rows16(const float* __restrict__ x, const int64_t* __restrict__ t_,
                                                           const float* __restrict__ e_, int B, int K, int from_logits,

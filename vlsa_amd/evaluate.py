@@ -83,10 +83,15 @@ class SurvEvaluator:
     """``NLLSurv_Evaluator(prediction_type, backend != 'SurvivalEVAL')`` on the device.  ``compute`` takes the reference's ``data``
     dict with DEVICE tensors -- ``'y'`` [M, 2] = (t, e); ``'raw_y_hat'`` [M, K] logits (preferred: the converter is fused into the
     launch), else ``'y_hat'``; ``'avg_y_hat'`` replaces the prediction as in the reference; ``'uid'`` is ignored -- and returns the
-    reference's keys as Python floats.  ``alpha`` / ``eps``: of ``loss_mle`` (the reference loads it with its defaults, 0 and 1e-7)."""
+    reference's keys as Python floats.  ``alpha`` / ``eps``: of ``loss_mle`` (the reference loads it with its defaults, 0 and 1e-7).
+
+    Ext losses (``kws_ext_loss``: the handler's loss dict, the reference's objects or this package's -- attributes only): SurvIFMLE /
+    SurvEMD on incidences come out of the rows launch; SurvMLE / SurvEMD on hazards and SurvT2I under either type out of the launches of
+    ``vlsa_amd.losses`` (csrc/surv_objectives.hip), one ``.item()`` each; anything else is called as the reference calls it."""
 
     valid_metrics = ["c_index", "loss", "loss_mle", "loss_mle_org"]
     fused_ext_losses = ("SurvIFMLE", "SurvEMD")
+    hazard_ext_losses = ("SurvMLE", "SurvEMD")          # under prediction_type = 'hazard': the per-sample launch of vlsa_amd.losses
 
     def __init__(self, prediction_type: str, backend: str = "none", alpha: float = 0.0, eps: float = 1e-7, tied_tol: float = 1e-8, **kws):
         assert prediction_type in ["hazard", "incidence"], "The `prediction_type` should be hazard or incidence."
@@ -101,12 +106,32 @@ class SurvEvaluator:
             assert m in self.valid_metrics, f"[SurvEvaluator] got an invalid metric name: {m}."
 
     # ---- the launches ----
+    _module_attrs = {"SurvMLE": ("alpha", "eps"), "SurvEMD": ("p", "raw_distance"), "SurvT2I": ("loss", "reduction")}
+
+    def _by_module(self, name, func):
+        """a loss OBJECT named SurvT2I, or SurvMLE / SurvEMD under 'hazard', carrying the attributes the launches read (a plain
+        callable under one of these names is called as the reference calls it)"""
+        if name != "SurvT2I" and not (self.type == "hazard" and name in self.hazard_ext_losses):
+            return False
+        return all(hasattr(func, a) for a in self._module_attrs[name])
+
     def _ext_spec(self, kws_ext_loss, kws):
-        """(ext_mask, alpha, eps, p, raw_distance, w_ifmle, w_emd) of the ext losses the rows kernel evaluates, and the names left to
-        be called as the reference calls them"""
-        spec = dict(mask=0, alpha=0.0, eps=1e-7, p=2, raw=1, w_ifmle=0.0, w_emd=0.0)
+        """(ext_mask, alpha, eps, p, raw_distance, w_ifmle, w_emd) of the ext losses the rows kernel evaluates, `modules` = the names
+        the launches of vlsa_amd.losses evaluate (SurvMLE / SurvEMD on hazards, SurvT2I), and the names left to be called as the
+        reference calls them"""
+        spec = dict(mask=0, alpha=0.0, eps=1e-7, p=2, raw=1, w_ifmle=0.0, w_emd=0.0, modules=[])
         other = []
         for name, func in (kws_ext_loss or {}).items():
+            if self._by_module(name, func):
+                # evaluated by the launches of vlsa_amd.losses (surv_objectives.hip), whichever class the handler's object is
+                if name != "SurvT2I" and getattr(func, "reduction", "mean") != "mean":
+                    raise NotImplementedError(f"{name}: the evaluator covers reduction = 'mean', got {func.reduction!r}")
+                if name == "SurvEMD" and func.p not in (1, 2):
+                    raise NotImplementedError(f"SurvEMD: the kernel covers p = 1 and p = 2, got {func.p!r}")
+                if name == "SurvT2I" and func.loss not in ("CL", "KL"):
+                    raise NotImplementedError(f"Expected loss = CL or KL, but got {func.loss}.")
+                spec["modules"].append(name)
+                continue
             if name not in self.fused_ext_losses:
                 other.append(name)
                 continue
@@ -159,7 +184,21 @@ class SurvEvaluator:
         if "c_index" in metrics:
             nat.check(lib.vlsa_concordance_pairs(_p(tm), _p(e), _p(est), M, self.tied_tol, _p(res[_COUNTERS]), 0, _stream()),
                       "vlsa_concordance_pairs")
-        return res, est, surv, x, kind, t, e, other
+        return res, est, surv, x, kind, t, e, other + spec["modules"]
+
+    def _module_loss(self, name, func, data, x, kind, t, e, ls):
+        """An ext loss of ``_ext_spec``'s `modules` as a 0-dim device tensor, unweighted: SurvMLE / SurvEMD on the hazards (the sigmoid
+        fused in where x holds raw logits), SurvT2I on ``data['raw_y_hat']``"""
+        from . import losses as L
+        if name == "SurvT2I":
+            raw = data.get("raw_y_hat")
+            if raw is None:
+                raise ValueError("SurvT2I is evaluated on data['raw_y_hat']")
+            return L._launch_t2i(_as_tensor(raw), t, e, ls, False, func.loss, func.reduction, 1.0, want_grad=False)[0]
+        conv = nat.CONV_SIGMOID if kind == nat.EVAL_RAW else nat.CONV_NONE
+        if name == "SurvMLE":
+            return L._launch_terms(x, t, e, conv, nat.SURV_MLE, None, func.alpha, func.eps, 2, True, 1.0, 0.0, want_grad=False)[0].mean()
+        return L._launch_terms(x, t, e, conv, nat.SURV_MLE, ls, 0.0, 1e-7, func.p, func.raw_distance, 0.0, 1.0, want_grad=False)[1].mean()
 
     def compute_device(self, data, metrics, kws_ext_loss=None, **kws):
         """The launches of ``compute`` without the copy: the device result buffer, 16 float64 words laid out as ``vlsa_hip.h`` says
@@ -211,6 +250,8 @@ class SurvEvaluator:
                 func = kws_ext_loss[name]
                 if name == "QueryDiv":
                     loss = weight(name) * func()
+                elif self._by_module(name, func):
+                    loss = weight(name) * self._module_loss(name, func, data, x, kind, t, e, ls)
                 elif name == "SurvT2I":
                     loss = weight(name) * func(data.get("raw_y_hat"), t1, e1, ls)
                 else:
