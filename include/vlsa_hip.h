@@ -679,6 +679,102 @@ int vlsa_concordance_pairs(const double* time, const float* e, const double* est
                            int zero_first, void* stream);
 
 /*
+ * The continuous survival heads' objective (runner/sa_handler.py: loss_type SurvPLE, or recon_loss / rank_loss / MSE_loss, on a one-column
+ * prediction with net_output_converter None) -- value, every term's value and gradient in ONE launch of one workgroup, which reads no
+ * host data (capturable).  1 <= B <= 4096 (VLSA_EUNSUPPORTED above).  No atomics; every sum has one fixed order: two runs give the same bits.
+ *   pred [B] fp32    contiguous (a [B, 1] tensor is the same memory)
+ *   time [B]         fp32 (time_dtype = VLSA_PAIR_TIME_F32) or fp64 (VLSA_PAIR_TIME_F64); compared and subtracted in float64
+ *   e [B] fp32       1 = event, 0 = censored.  Any other value is OUT OF CONTRACT: the terms weigh by e, rank_loss tests e == 1
+ *   w_*              the terms' weights; a term whose weight is 0 is not computed: its value word reads 0 and it adds nothing
+ *   SurvPLE          (loss/loss_surv.py:189-209) theta = min(pred, 10); D_i = sum_{j: T_j >= T_i} exp theta_j, ties included;
+ *                    value = -(1/B) sum_i e_i (theta_i - log D_i), the log-sum-exp shifted by the batch's largest theta;
+ *                    d value / d pred_k = -(1/B) (e_k - exp theta_k * sum_{i: e_i = 1, T_i <= T_k} 1 / D_i) where pred_k <= 10, else 0.
+ *                    A batch without an event gives +0 (the reference: -0)
+ *   rank_loss        (lines 33-70, add_weight = False) the mean of relu(rank_gamma + p_i - p_j)^norm over the pairs with t_i < t_j and
+ *                    e_i == 1; the pair count is an integer; without a pair, value and gradient are 0
+ *   recon_loss       (lines 11-31) mean_i (1 - alpha) (obs_i + cen_i) + alpha obs_i, obs = e |p - t|, cen = (1 - e) relu(gamma - (p - t)),
+ *                    both squared under VLSA_PAIR_NORM_L2
+ *   MSE_loss         (lines 72-86) mean_i e (p - t)^2, plus (1 - e) (p - t)^2 where mse_include_censored != 0
+ *                    abs and relu have derivative 0 at 0, as torch has them
+ *   objective [VLSA_PAIR_OBJ_WORDS] fp32: sum of weight * term at VLSA_PAIR_OBJ_TOTAL, each term's unweighted value behind it, and the
+ *                    number of rank pairs (exact: below 2^24)
+ *   grad [B] fp32    d objective[0] / d pred, or NULL to skip
+ * A bad pointer, size, dtype or norm code is VLSA_EINVAL; nothing is launched then.
+ */
+#define VLSA_PAIR_TIME_F32 0
+#define VLSA_PAIR_TIME_F64 1
+#define VLSA_PAIR_NORM_L1 1
+#define VLSA_PAIR_NORM_L2 2
+#define VLSA_PAIR_MAX_B 4096
+#define VLSA_PAIR_OBJ_WORDS 6
+#define VLSA_PAIR_OBJ_TOTAL 0
+#define VLSA_PAIR_OBJ_PLE 1
+#define VLSA_PAIR_OBJ_RANK 2
+#define VLSA_PAIR_OBJ_RECON 3
+#define VLSA_PAIR_OBJ_MSE 4
+#define VLSA_PAIR_OBJ_PAIRS 5
+int vlsa_surv_pair_objective(const float* pred, const void* time, int time_dtype, const float* e, int B, double w_ple, double w_rank,
+                             double w_recon, double w_mse, double rank_gamma, int rank_norm, double recon_alpha, double recon_gamma,
+                             int recon_norm, int mse_include_censored, float* objective, float* grad, void* stream);
+
+/*
+ * The same two passes for a split of 1 <= M <= VLSA_EVAL_MAX_M samples (VLSA_EUNSUPPORTED above), everything float64: what
+ * CoxSurv_Evaluator (eval/evaluator_surv.py:238-378) needs beyond Harrell's C -- its loss_ple and the Breslow baseline of
+ * eval/utils_coxph.py:193-236.  Each output element is summed by one owner in ascending sample order: no atomics, bit-reproducible.
+ * vlsa_cox_risk_sets: D[i] = sum_{j: time_j >= time_i} exp(min(theta_j, cap)), ties included.  theta [M] fp32, time [M] f64, e [M] fp32
+ *   (not read: the risk set holds censored samples too), cap = 10.0 for SurvPLE or +inf for Breslow (exp is NOT shifted here: a float64
+ *   exp overflows above 709 only).  A NaN cap is VLSA_EINVAL.
+ * vlsa_cox_cum_hazard: H[q] = sum_{i: e_i != 0, time_i <= query_q} e_i / D[i] for Q queries (1 <= Q <= VLSA_EVAL_MAX_M): the samples' own
+ *   times for the loss's gradient, the training split's unique times for the baseline (with cap = +inf: Breslow's cumulative baseline
+ *   hazard).  e: 0 / 1, anything else is out of contract.
+ * vlsa_cox_finish: result [VLSA_CEVAL_RESULT_WORDS] 8-byte words.  Doubles at words 0 .. 3: sum_i e_i (min(theta_i, cap) - log D[i]) at
+ *   VLSA_CEVAL_SUM_PLE (SurvPLE = -sum / M), the number of events, of non-finite theta, and M.  Words 4 .. 15 are ZEROED, among them
+ *   the five uint64 pair counters at VLSA_CEVAL_CONCORDANT .. VLSA_CEVAL_COMPARABLE.  For Harrell's C, vlsa_concordance_pairs follows
+ *   on the SAME stream with counters = &result[VLSA_CEVAL_CONCORDANT] and zero_first = 0; the estimate it ranks by is -theta
+ *   (eval/cindex.py:29-35).
+ */
+#define VLSA_CEVAL_RESULT_WORDS 16
+#define VLSA_CEVAL_SUM_PLE 0
+#define VLSA_CEVAL_EVENTS 1
+#define VLSA_CEVAL_NONFINITE 2
+#define VLSA_CEVAL_M 3
+#define VLSA_CEVAL_CONCORDANT 8
+#define VLSA_CEVAL_COMPARABLE 12
+int vlsa_cox_risk_sets(const float* theta, const double* time, const float* e, int M, double cap, double* D, void* stream);
+int vlsa_cox_cum_hazard(const double* time, const float* e, const double* D, int M, const double* query, int Q, double* H, void* stream);
+int vlsa_cox_finish(const float* theta, const float* e, const double* D, int M, double cap, double* result, void* stream);
+/*
+ * vlsa_reg_eval: the sums of RegSurv_Evaluator (eval/evaluator_surv.py:381-466) over a split in two launches, float64: every pair for
+ * rank_loss (options as vlsa_surv_pair_objective's), then one workgroup for the rest.  1 <= M <= VLSA_EVAL_MAX_M.
+ *   pred [M] fp32, time [M] f64, e [M] fp32 (0 / 1)
+ *   partial [2 M]    device scratch: per-sample rank numerators, then per-sample pair counts; added in sample order
+ *   rank_grad [M]    out, may be NULL: d (rank numerator) / d pred_i; divide by the pair count
+ *   result [VLSA_REVAL_RESULT_WORDS] 8-byte words: doubles -- the rank numerator and pair count; sum_i recon_loss_i at recon_alpha and
+ *                    at alpha = 0; sum |t - p| / end_time and sum (p - t) / end_time over e == 1, sum relu(t - p) / end_time and
+ *                    sum -relu(t - p) / end_time over e == 0 (lines 436-458) with the two group sizes; the number of non-finite
+ *                    predictions, of samples with e != 0, and M -- and the five uint64 pair counters at VLSA_REVAL_CONCORDANT ..,
+ *                    ZEROED here as vlsa_cox_finish zeroes its own
+ */
+#define VLSA_REVAL_RESULT_WORDS 18
+#define VLSA_REVAL_RANK_NUM 0
+#define VLSA_REVAL_RANK_PAIRS 1
+#define VLSA_REVAL_RECON 2
+#define VLSA_REVAL_RECON_ORG 3
+#define VLSA_REVAL_EVT_RAE 4
+#define VLSA_REVAL_NOEVT_RAE 5
+#define VLSA_REVAL_EVT_NRE 6
+#define VLSA_REVAL_NOEVT_NRE 7
+#define VLSA_REVAL_CONCORDANT 8
+#define VLSA_REVAL_COMPARABLE 12
+#define VLSA_REVAL_N_EVT 13
+#define VLSA_REVAL_N_NOEVT 14
+#define VLSA_REVAL_NONFINITE 15
+#define VLSA_REVAL_EVENTS 16
+#define VLSA_REVAL_M 17
+int vlsa_reg_eval(const float* pred, const double* time, const float* e, int M, double rank_gamma, int rank_norm, double recon_alpha,
+                  double recon_gamma, int recon_norm, double end_time, double* partial, double* rank_grad, double* result, void* stream);
+
+/*
  * The optimizer of the training step in ONE launch: torch.optim.Adam's update (runner/vlsa_handler.py:283-289 builds
  * optim.Adam(lr, weight_decay) through optim_factory.py:25-60; amsgrad = False, maximize = False, L2 weight decay added to the
  * gradient) over n_tensors fp32 tensors.  tensors: HOST array (read during the call: by-value kernel arguments); hyper: DEVICE float

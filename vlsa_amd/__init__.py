@@ -5,8 +5,8 @@ in hand-written HIP kernels behind the C ABI of include/vlsa_hip.h.  There is no
 """
 from ._native import VlsaNativeError  # noqa: F401
 
-__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA", "SurvEvaluator", "concordance_index_censored", "concordance_counts",
-           "SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective"]
+__all__ = ["VlsaNativeError", "DeepAttnMISL", "ILRA", "SurvEvaluator", "CoxSurvEvaluator", "RegSurvEvaluator", "concordance_index_censored", "concordance_counts",
+           "SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective", "SurvPLE", "rank_loss", "recon_loss", "MSE_loss", "SurvPairObjective"]
 
 
 def __getattr__(name):
@@ -16,10 +16,10 @@ def __getattr__(name):
     if name == "ILRA":
         from .deepmil import ILRA
         return ILRA
-    if name in ("SurvEvaluator", "concordance_index_censored", "concordance_counts"):
+    if name in ("SurvEvaluator", "CoxSurvEvaluator", "RegSurvEvaluator", "concordance_index_censored", "concordance_counts"):
         from . import evaluate
         return getattr(evaluate, name)
-    if name in ("SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective"):
+    if name in ("SurvIFMLE", "SurvMLE", "SurvEMD", "SurvT2I", "SurvObjective", "SurvPLE", "rank_loss", "recon_loss", "MSE_loss", "SurvPairObjective"):
         from . import losses
         return getattr(losses, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

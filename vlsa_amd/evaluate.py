@@ -6,6 +6,9 @@ buffer; Harrell's C is formed on the host from the exact counts.  No CPU fallbac
 
 What stays on the host: the SurvivalEVAL metrics (C on the mean survival time, IBS, MAE, D-calibration), which go through splines and
 Kaplan-Meier fits of the training set; ``compute(..., ret_survival=True)`` hands back the clamped survival curves for them.
+
+``CoxSurvEvaluator`` and ``RegSurvEvaluator`` are the reference's ``Cox`` and ``Reg`` evaluators for a one-column prediction (the
+launches of ``csrc/surv_pairs.hip``), with ``compute``, ``compute_device`` and ``read`` in the same manner.
 """
 from __future__ import annotations
 
@@ -265,3 +268,218 @@ class SurvEvaluator:
         if ret_risk:
             out["risk"] = est
         return out
+
+
+# ---- the continuous heads: CoxSurv_Evaluator and RegSurv_Evaluator (eval/evaluator_surv.py:238-466) on a one-column prediction ----
+def _column(data, M=None):
+    """(y_hat [M] fp32, t [M] float64, e [M] fp32) of the reference's ``data`` dict: 'avg_y_hat' replaces 'y_hat' as in the reference"""
+    y = _as_tensor(data["y"])
+    x = _as_tensor(data["avg_y_hat"] if "avg_y_hat" in data else data["y_hat"])
+    _need_gpu(x, y)
+    if y.dim() != 2 or y.shape[1] != 2 or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] != 1):
+        raise ValueError("expected a one-column prediction [M] or [M, 1] and labels 'y' [M, 2] = (t, e)")
+    x = x.detach().reshape(-1).float().contiguous()
+    M = x.numel()
+    if M < 1:
+        raise ValueError("Need a minimum of two samples")
+    t = y[:, 0].detach().to(device=x.device, dtype=torch.float64).contiguous()
+    e = y[:, 1].detach().to(device=x.device, dtype=torch.float32).contiguous()
+    if t.numel() != M:
+        raise ValueError("t and e must hold one entry per sample")
+    return x, t, e
+
+
+def _check_cindex(nonfinite, M, events):
+    """the reference's order of refusals: check_array, then eval/cindex.py:78-82, then 118-120 (no comparable pair: ``_cindex``)"""
+    if nonfinite != 0:
+        raise ValueError("Input contains NaN or infinity.")
+    if M < 2:
+        raise ValueError("Need a minimum of two samples")
+    if events == 0:
+        raise ValueError("All samples are censored")
+
+
+def cox_risk_sets(theta, t, e, cap=10.0):
+    """D [M] float64 = sum_{j: t_j >= t_i} exp(min(theta_j, cap)) (``vlsa_cox_risk_sets``); theta fp32, t float64, e fp32, contiguous"""
+    lib = nat.load()
+    D = torch.empty(theta.numel(), dtype=torch.float64, device=theta.device)
+    nat.check(lib.vlsa_cox_risk_sets(_p(theta), _p(t), _p(e), theta.numel(), float(cap), _p(D), _stream()), "vlsa_cox_risk_sets")
+    return D
+
+
+def cox_cum_hazard(t, e, D, query):
+    """H [Q] float64 = sum_{i: e_i = 1, t_i <= query_q} 1 / D_i (``vlsa_cox_cum_hazard``)"""
+    lib = nat.load()
+    query = query.to(dtype=torch.float64).contiguous()
+    H = torch.empty(query.numel(), dtype=torch.float64, device=t.device)
+    nat.check(lib.vlsa_cox_cum_hazard(_p(t), _p(e), _p(D), t.numel(), _p(query), query.numel(), _p(H), _stream()), "vlsa_cox_cum_hazard")
+    return H
+
+
+class CoxSurvEvaluator:
+    """``CoxSurv_Evaluator(backend != 'SurvivalEVAL')`` (eval/evaluator_surv.py:238-378) on the device: ``compute`` takes the reference's
+    ``data`` dict with DEVICE tensors -- ``'y'`` [M, 2] = (t, e), ``'y_hat'`` or ``'avg_y_hat'`` [M, 1] or [M], ``'name'``; ``'uid'`` is
+    ignored (the labels come from ``'y'``, not from a meta-data table) -- and returns ``c_index``, ``loss`` and ``loss_ple`` as Python
+    floats.  Three launches -- the risk-set sums, the finishing sums, the pair counts -- and ONE copy of a 128-byte result buffer.
+
+    ``c_index`` mirrors the reference's ``_c_index``: Harrell's C of the estimate ``-y_hat`` (eval/cindex.py:29-35).  ``SurvPLE`` drives
+    y_hat UP for early events, so a head it trained scores 1 - C under this key; ``concordance_index_censored(e, t, y_hat)`` gives the
+    other sign.  The Breslow baseline (eval/utils_coxph.py:193-236, theta uncapped) is fitted by ``fit_baseline`` -- which ``compute``
+    runs itself when ``data['name'] == 'train'``, as the reference does -- with one ``torch.unique``, so one synchronisation per fit;
+    ``compute(..., ret_survival=True)`` then adds ``'time_points'`` [U] and ``'survival_hat'`` [M, U] = exp(-H_u exp(y_hat_m)), float64,
+    the curves ``_pre_compute`` hands SurvivalEVAL, and raises ``RuntimeError`` before a fit."""
+
+    valid_metrics = ["c_index", "loss", "loss_ple"]
+    CAP = 10.0                                # SurvPLE's CONSTANT
+
+    def __init__(self, backend: str = "none", tied_tol: float = 1e-8, **kws):
+        if backend == "SurvivalEVAL":
+            raise NotImplementedError("the SurvivalEVAL metrics stay on the host: compute(..., ret_survival=True) returns the survival "
+                                      "curves they start from")
+        self.backend, self.kws, self.tied_tol = backend, kws, float(tied_tol)
+        self.time_points = self.cum_hazard = None
+
+    def _check_metrics(self, metrics):
+        for m in metrics:
+            assert m in self.valid_metrics, f"[CoxSurvEvaluator] got an invalid metric name: {m}."
+
+    def fit_baseline(self, y_hat, t, e):
+        """Breslow's estimator on a training split: stores its sorted unique times [U] and the cumulative baseline hazard there [U]"""
+        y = torch.stack([_as_tensor(t).reshape(-1).double(), _as_tensor(e).reshape(-1).double()], dim=1)
+        return self._fit(*_column({"y_hat": y_hat, "y": y}))
+
+    def _fit(self, x, t, e):
+        """``fit_baseline`` on converted tensors (``_column``)"""
+        D = cox_risk_sets(x, t, e, float("inf"))
+        self.time_points = torch.unique(t)        # sorted; the one synchronisation of a fit
+        self.cum_hazard = cox_cum_hazard(t, e, D, self.time_points)
+        return self
+
+    def survival(self, y_hat):
+        """[M, U] float64 curves S(u | x_m) = S_0(u) ^ exp(y_hat_m) at ``self.time_points``"""
+        if self.cum_hazard is None:
+            raise RuntimeError("CoxSurvEvaluator: no baseline yet -- call fit_baseline, or compute on data whose 'name' is 'train'")
+        return torch.exp(-self.cum_hazard.view(1, -1) * torch.exp(_as_tensor(y_hat).detach().reshape(-1, 1).double()))
+
+    def _launch(self, x, t, e, metrics):
+        """the launches on converted tensors (``_column``): the device result buffer"""
+        lib = nat.load()
+        M = x.numel()
+        res = torch.empty(nat.CEVAL_RESULT_WORDS, dtype=torch.float64, device=x.device)
+        D = cox_risk_sets(x, t, e, self.CAP)
+        nat.check(lib.vlsa_cox_finish(_p(x), _p(e), _p(D), M, self.CAP, _p(res), _stream()), "vlsa_cox_finish")
+        if "c_index" in metrics:
+            est = (-x).double()
+            nat.check(lib.vlsa_concordance_pairs(_p(t), _p(e), _p(est), M, self.tied_tol, _p(res[nat.CEVAL_CONCORDANT:]), 0, _stream()),
+                      "vlsa_concordance_pairs")
+        return res
+
+    def compute_device(self, data, metrics, **kws):
+        """The launches of ``compute`` without the copy (and without a baseline fit): the device result buffer, laid out as
+        ``vlsa_hip.h`` says (``VLSA_CEVAL_*``), for a loop that reads it later with ``read``."""
+        self._check_metrics(metrics)
+        return self._launch(*_column(data), metrics)
+
+    def read(self, result, metrics):
+        host = result.cpu()
+        sums = host.tolist()
+        counts = host[nat.CEVAL_CONCORDANT:nat.CEVAL_COMPARABLE + 1].view(torch.int64).tolist()
+        M = int(sums[nat.CEVAL_M])
+        out = {}
+        for m in metrics:
+            if m == "c_index":
+                _check_cindex(sums[nat.CEVAL_NONFINITE], M, sums[nat.CEVAL_EVENTS])
+                out[m] = _cindex(*counts)[0]
+            else:
+                out[m] = 0.0 - sums[nat.CEVAL_SUM_PLE] / M
+        self.counts = dict(zip(("concordant", "discordant", "tied_risk", "tied_time", "comparable"), counts))
+        return out
+
+    def compute(self, data, metrics, ret_survival=False, **kws):
+        self._check_metrics(metrics)
+        x, t, e = _column(data)                  # the one conversion of the labels; the fit and the launches share it
+        if data.get("name") == "train":
+            self._fit(x, t, e)
+        out = self.read(self._launch(x, t, e, metrics), metrics)
+        if ret_survival:
+            out["survival_hat"] = self.survival(x)
+            out["time_points"] = self.time_points
+        return out
+
+
+def _fp32_reciprocal(n):
+    """1 / n as the reference's rank_loss forms it: its pair weights ``pair_mask.float() / pair_mask.float().sum()`` are fp32 whatever
+    the prediction's dtype, so the mean it returns is the sum times the fp32 rounding of 1 / n (loss/loss_surv.py:50-60)"""
+    return float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32))
+
+
+class RegSurvEvaluator:
+    """``RegSurv_Evaluator(end_time=...)`` (eval/evaluator_surv.py:381-466) on the device: its nine metrics from ``vlsa_reg_eval`` (every
+    pair for ``loss_rank``, one workgroup for the rest, float64) and ``vlsa_concordance_pairs``, ONE copy of a 144-byte result buffer.
+    ``alpha`` / ``gamma`` / ``norm``: of ``loss_recon`` (the reference loads it with its defaults, where it equals ``loss_recon_org``);
+    ``rank_gamma`` / ``rank_norm``: of ``loss_rank``, which is the exact pair sum times the fp32 rounding of 1 / pairs, as the reference's
+    fp32 pair weights make it (within 6e-8 of the mean, relative; exact counts up to 2^24 pairs).  An empty event or non-event group
+    gives NaN, as the reference's mean of nothing.
+
+    ``c_index``: the reference's own ``_c_index`` cannot run -- it passes ``type_pred='survival_time'`` into ``concordance_index``, which
+    asserts ``'hazard_ratio'`` for a one-column prediction (eval/cindex.py:29-31).  This returns what the call yields without the
+    assertion: Harrell's C of the estimate ``-y_hat``."""
+
+    valid_metrics = ["c_index", "loss", "loss_rank", "loss_recon", "loss_recon_org", "event_t_rae", "nonevent_t_rae", "event_t_nre",
+                     "nonevent_t_nre"]
+
+    def __init__(self, end_time=None, alpha=0.0, gamma=1.0, norm="l1", rank_gamma=1.0, rank_norm="l1", tied_tol=1e-8, **kws):
+        if end_time is None:
+            raise KeyError("end_time")             # the reference reads kws['end_time']
+        from .losses import _NORM
+        if rank_norm not in _NORM:
+            raise NotImplementedError("Arg. `norm` expected l1/l2, but got {}".format(rank_norm))
+        self.end_time, self.kws, self.tied_tol = float(end_time), kws, float(tied_tol)
+        self._spec = (float(rank_gamma), _NORM[rank_norm], float(alpha), float(gamma), _NORM["l2" if norm == "l2" else "l1"], self.end_time)
+
+    def _check_metrics(self, metrics):
+        for m in metrics:
+            assert m in self.valid_metrics
+
+    def compute_device(self, data, metrics, **kws):
+        """The launches of ``compute`` without the copy: the device result buffer (``VLSA_REVAL_*``) for ``read``."""
+        self._check_metrics(metrics)
+        x, t, e = _column(data)
+        lib = nat.load()
+        M = x.numel()
+        buf = torch.empty(nat.REVAL_RESULT_WORDS + 2 * M, dtype=torch.float64, device=x.device)       # result words | per-sample partials
+        res = buf[:nat.REVAL_RESULT_WORDS]
+        nat.check(lib.vlsa_reg_eval(_p(x), _p(t), _p(e), M, *self._spec, _p(buf[nat.REVAL_RESULT_WORDS:]), None, _p(res), _stream()),
+                  "vlsa_reg_eval")
+        if "c_index" in metrics:
+            est = (-x).double()
+            nat.check(lib.vlsa_concordance_pairs(_p(t), _p(e), _p(est), M, self.tied_tol, _p(res[nat.REVAL_CONCORDANT:]), 0, _stream()),
+                      "vlsa_concordance_pairs")
+        return res
+
+    def read(self, result, metrics):
+        host = result.cpu()
+        s = host.tolist()
+        counts = host[nat.REVAL_CONCORDANT:nat.REVAL_COMPARABLE + 1].view(torch.int64).tolist()
+        M = int(s[nat.REVAL_M])
+        mean = lambda total, n: total / n if n else float("nan")  # noqa: E731
+        values = {"loss": lambda: s[nat.REVAL_RECON_ORG] / M, "loss_recon_org": lambda: s[nat.REVAL_RECON_ORG] / M,
+                  "loss_recon": lambda: s[nat.REVAL_RECON] / M,
+                  "loss_rank": lambda: s[nat.REVAL_RANK_NUM] * _fp32_reciprocal(s[nat.REVAL_RANK_PAIRS]) if s[nat.REVAL_RANK_PAIRS] else 0.0,
+                  "event_t_rae": lambda: mean(s[nat.REVAL_EVT_RAE], s[nat.REVAL_N_EVT]),
+                  "nonevent_t_rae": lambda: mean(s[nat.REVAL_NOEVT_RAE], s[nat.REVAL_N_NOEVT]),
+                  "event_t_nre": lambda: mean(s[nat.REVAL_EVT_NRE], s[nat.REVAL_N_EVT]),
+                  "nonevent_t_nre": lambda: mean(s[nat.REVAL_NOEVT_NRE], s[nat.REVAL_N_NOEVT])}
+        out = {}
+        for m in metrics:
+            if m == "c_index":
+                _check_cindex(s[nat.REVAL_NONFINITE], M, s[nat.REVAL_EVENTS])
+                out[m] = _cindex(*counts)[0]
+            else:
+                out[m] = values[m]()
+        self.counts = dict(zip(("concordant", "discordant", "tied_risk", "tied_time", "comparable"), counts))
+        self.rank_pairs = int(s[nat.REVAL_RANK_PAIRS])
+        return out
+
+    def compute(self, data, metrics, **kws):
+        return self.read(self.compute_device(data, metrics), metrics)

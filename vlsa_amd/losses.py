@@ -8,6 +8,10 @@ The handler's other objectives (runner/vlsa_handler.py:33-41, loss/utils.py:52-7
 ``csrc/surv_objectives.hip``: the hazard family -- ``SurvMLE`` (loss/loss_surv.py:89-124) behind the sigmoid converter, ``SurvEMD`` on
 the hazards -- and ``SurvT2I`` (loss/loss_surv_ext.py:126-195).  ``SurvObjective(converter=..., weight_mle=..., weight_t2i=...)`` takes
 them in one launch too; with its defaults it issues exactly the launch it always issued.
+
+The continuous heads of runner/sa_handler.py -- ``SurvPLE`` (loss/loss_surv.py:172-209), ``rank_loss``, ``recon_loss`` and ``MSE_loss``
+(lines 11-86) on a one-column prediction -- come from the launch of ``csrc/surv_pairs.hip``; ``SurvPairObjective`` is their
+``calc_objective_loss``.
 """
 from __future__ import annotations
 
@@ -360,3 +364,204 @@ class SurvObjective(nn.Module):
             v2, g2 = _launch_t2i(raw_pred, t, e, log_logit_scale, True, t2i_loss, t2i_reduction, w_t2i)
             value, g = value + v2, g + g2
         return value, g
+
+
+# ---- the continuous heads (runner/sa_handler.py: loss_type SurvPLE, or recon_loss / rank_loss / MSE_loss, on a one-column prediction
+# with net_output_converter None): csrc/surv_pairs.hip, value + every term's value + gradient in ONE launch up to 4096 samples,
+# the split launches above ----
+_NORM = {"l1": nat.PAIR_NORM_L1, "l2": nat.PAIR_NORM_L2}
+PAIR_TERMS = {"SurvPLE": nat.PAIR_OBJ_PLE, "rank_loss": nat.PAIR_OBJ_RANK, "recon_loss": nat.PAIR_OBJ_RECON, "MSE_loss": nat.PAIR_OBJ_MSE}
+
+
+def _pair_spec(w_ple=0.0, w_rank=0.0, w_recon=0.0, w_mse=0.0, rank_gamma=1.0, rank_norm="l1", recon_alpha=0.0, recon_gamma=1.0,
+               recon_norm="l1", mse_include_censored=False):
+    """the launch's arguments behind the tensors; recon_loss squares under 'l2' and takes anything else as l1, as the reference does"""
+    if rank_norm not in _NORM:
+        raise NotImplementedError("Arg. `norm` expected l1/l2, but got {}".format(rank_norm))
+    return (float(w_ple), float(w_rank), float(w_recon), float(w_mse), float(rank_gamma), _NORM[rank_norm], float(recon_alpha),
+            float(recon_gamma), _NORM["l2" if recon_norm == "l2" else "l1"], int(bool(mse_include_censored)))
+
+
+def _launch_pair(pred, t, e, spec, want_grad=True):
+    """``vlsa_surv_pair_objective``: (the launch's fp32 result words [PAIR_OBJ_WORDS] -- the objective, the four terms, the number of
+    rank pairs --, d objective / d pred in pred's shape or None).  pred: [B] or [B, 1]; t: fp32 or fp64 stay as they are, any other
+    dtype is compared as fp64; e: 0 / 1."""
+    _need_gpu(pred)
+    if pred.dim() not in (1, 2) or (pred.dim() == 2 and pred.shape[1] != 1):
+        raise ValueError("expected a one-column prediction, [B] or [B, 1]")
+    lib = nat.load()
+    x = pred.detach().float().contiguous()
+    B = x.numel()
+    t = t.detach().reshape(-1).to(device=x.device)
+    t = (t if t.dtype in (torch.float32, torch.float64) else t.double()).contiguous()
+    e = e.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
+    if t.numel() != B or e.numel() != B:
+        raise ValueError("t and e must hold one entry per sample")
+    out = torch.empty(nat.PAIR_OBJ_WORDS + (B if want_grad else 0), dtype=torch.float32, device=x.device)     # words | gradient: one allocation
+    g = out[nat.PAIR_OBJ_WORDS:] if want_grad else None
+    nat.check(lib.vlsa_surv_pair_objective(_p(x), _p(t), nat.PAIR_TIME_F64 if t.dtype == torch.float64 else nat.PAIR_TIME_F32, _p(e), B, *spec,
+                                           _p(out), _p(g), _stream()), "vlsa_surv_pair_objective")
+    return out[:nat.PAIR_OBJ_WORDS], (g.view(pred.shape) if want_grad else None)
+
+
+def _launch_pair_split(pred, t, e, spec, want_grad=True):
+    """``_launch_pair`` for a batch above ``PAIR_MAX_B`` samples: the split launches of csrc/surv_pairs.hip -- the risk-set sums and the
+    cumulative hazard at the samples' own times (SurvPLE), every rank pair with the per-sample gradient (``vlsa_reg_eval``) -- in
+    float64, joined by element-wise torch ops on [B] vectors (recon_loss and MSE_loss are element-wise altogether).  No
+    synchronisation; the result words are fp32 as the one launch writes them."""
+    from .evaluate import cox_cum_hazard, cox_risk_sets
+    _need_gpu(pred)
+    if pred.dim() not in (1, 2) or (pred.dim() == 2 and pred.shape[1] != 1):
+        raise ValueError("expected a one-column prediction, [B] or [B, 1]")
+    lib = nat.load()
+    x = pred.detach().reshape(-1).float().contiguous()
+    B = x.numel()
+    t = t.detach().reshape(-1).to(device=x.device, dtype=torch.float64).contiguous()
+    e = e.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
+    if t.numel() != B or e.numel() != B:
+        raise ValueError("t and e must hold one entry per sample")
+    w_ple, w_rank, w_recon, w_mse, rank_gamma, rank_norm, recon_alpha, recon_gamma, recon_norm, mse_censored = spec
+    p, ed = x.double(), e.double()
+    words = torch.zeros(nat.PAIR_OBJ_WORDS, dtype=torch.float64, device=x.device)
+    g = torch.zeros(B, dtype=torch.float64, device=x.device)
+    if w_ple != 0:
+        D = cox_risk_sets(x, t, e, 10.0)
+        res = torch.empty(nat.CEVAL_RESULT_WORDS, dtype=torch.float64, device=x.device)
+        nat.check(lib.vlsa_cox_finish(_p(x), _p(e), _p(D), B, 10.0, _p(res), _stream()), "vlsa_cox_finish")
+        words[nat.PAIR_OBJ_PLE] = 0.0 - res[nat.CEVAL_SUM_PLE] / B
+        if want_grad:
+            H = cox_cum_hazard(t, e, D, t)
+            g += w_ple * torch.where(x > 10.0, torch.zeros_like(p), -(ed - torch.exp(p.clamp(max=10.0)) * H) / B)
+    if w_rank != 0:
+        buf = torch.empty(nat.REVAL_RESULT_WORDS + 3 * B, dtype=torch.float64, device=x.device)     # result words | partials | gradient
+        res, rg = buf[:nat.REVAL_RESULT_WORDS], buf[nat.REVAL_RESULT_WORDS + 2 * B:]
+        nat.check(lib.vlsa_reg_eval(_p(x), _p(t), _p(e), B, rank_gamma, rank_norm, recon_alpha, recon_gamma, recon_norm, 1.0,
+                                    _p(buf[nat.REVAL_RESULT_WORDS:]), _p(rg), _p(res), _stream()), "vlsa_reg_eval")
+        pairs = res[nat.REVAL_RANK_PAIRS]
+        words[nat.PAIR_OBJ_RANK] = res[nat.REVAL_RANK_NUM] / pairs.clamp(min=1.0)       # no pair: the numerator is 0 too
+        words[nat.PAIR_OBJ_PAIRS] = pairs
+        g += w_rank * rg / pairs.clamp(min=1.0)
+    d = p - t
+    if w_recon != 0:
+        l2 = recon_norm == nat.PAIR_NORM_L2
+        x_c = recon_gamma - d
+        obs, cen = ed * d.abs(), (1.0 - ed) * x_c.clamp(min=0.0)
+        d_obs, d_cen = ed * torch.sign(d), -(1.0 - ed) * (x_c > 0)
+        if l2:
+            d_obs, d_cen, obs, cen = 2.0 * obs * d_obs, 2.0 * cen * d_cen, obs * obs, cen * cen
+        words[nat.PAIR_OBJ_RECON] = ((1.0 - recon_alpha) * (obs + cen) + recon_alpha * obs).sum() / B
+        g += w_recon * ((1.0 - recon_alpha) * (d_obs + d_cen) + recon_alpha * d_obs) / B
+    if w_mse != 0:
+        w = ed + (1.0 - ed if mse_censored else 0.0)
+        words[nat.PAIR_OBJ_MSE] = (w * d * d).sum() / B
+        g += w_mse * 2.0 * w * d / B
+    words[nat.PAIR_OBJ_TOTAL] = (w_ple * words[nat.PAIR_OBJ_PLE] + w_rank * words[nat.PAIR_OBJ_RANK] + w_recon * words[nat.PAIR_OBJ_RECON]
+                                 + w_mse * words[nat.PAIR_OBJ_MSE])
+    return words.float(), (g.float().view(pred.shape) if want_grad else None)
+
+
+def _pair_route(pred):
+    return _launch_pair if pred.numel() <= nat.PAIR_MAX_B else _launch_pair_split
+
+
+class _PairFn(torch.autograd.Function):
+    """one result word of the launch as a 0-dim tensor, differentiable w.r.t. the prediction only: the launch forward, one
+    multiplication backward"""
+
+    @staticmethod
+    def forward(ctx, pred, t, e, spec, word):
+        words, g = _pair_route(pred)(pred, t, e, spec)
+        ctx.save_for_backward(g)
+        return words[word]
+
+    @staticmethod
+    def backward(ctx, dl):
+        (g,) = ctx.saved_tensors
+        return dl * g, None, None, None, None
+
+
+def recon_loss(pred_t, t, e, alpha=0.0, gamma=1.0, norm="l1", cur_alpha=None, **kws):
+    """The reference's ``recon_loss`` (loss/loss_surv.py:11-31): mean_i (1 - alpha) (obs_i + cen_i) + alpha obs_i."""
+    spec = _pair_spec(w_recon=1.0, recon_alpha=alpha if cur_alpha is None else cur_alpha, recon_gamma=gamma, recon_norm=norm)
+    return _PairFn.apply(pred_t, t, e, spec, nat.PAIR_OBJ_RECON)
+
+
+def rank_loss(pred_t, t, e, gamma=1, norm="l1", add_weight=False, **kws):
+    """The reference's ``rank_loss`` (loss/loss_surv.py:33-70) without its three [B, B] matrices.  Two differences: a batch without a
+    pair gives a 0-dim zero whose gradient is zero (the reference: ``Tensor([0.])`` outside the graph), and ``add_weight=True`` is
+    refused -- its softmax weights carry a gradient of their own that the launch does not form."""
+    if add_weight:
+        raise NotImplementedError("rank_loss(add_weight=True) is not part of the launch")
+    return _PairFn.apply(pred_t, t, e, _pair_spec(w_rank=1.0, rank_gamma=gamma, rank_norm=norm), nat.PAIR_OBJ_RANK)
+
+
+def MSE_loss(pred_t, t, e, include_censored=False, **kws):
+    """The reference's ``MSE_loss`` (loss/loss_surv.py:72-86)."""
+    return _PairFn.apply(pred_t, t, e, _pair_spec(w_mse=1.0, mse_include_censored=include_censored), nat.PAIR_OBJ_MSE)
+
+
+class SurvPLE(nn.Module):
+    """The reference's ``SurvPLE`` (loss/loss_surv.py:172-209) without its B x B Python loop.  One difference: a batch without an event
+    gives ``0.`` where the reference gives ``-0.``."""
+
+    def __init__(self, **kws):
+        super().__init__()
+        self.CONSTANT = torch.tensor(10.0)      # the cap lives in the kernel; kept for a caller that reads it
+
+    def forward(self, y_hat, T, E):
+        return _PairFn.apply(y_hat, T, E, _pair_spec(w_ple=1.0), nat.PAIR_OBJ_PLE)
+
+
+class SurvPairObjective(nn.Module):
+    """``calc_objective_loss`` of the continuous heads (runner/sa_handler.py:172-180 with the identity converter): weight_ple * SurvPLE +
+    weight_rank * rank_loss + weight_recon * recon_loss + weight_mse * MSE_loss of a [B] or [B, 1] prediction, value and gradient in ONE
+    launch (``vlsa_surv_pair_objective``).  ``label``: [B, 2] = (t, e) as the handler passes it, or t and e separately.  Above 4096
+    samples the split launches take over (``_launch_pair_split``: float64 pair sums, torch adds).  The differences from the reference are those of
+    ``rank_loss`` and ``SurvPLE`` above.  After a call ``self.terms`` holds the launch's result words on the device (``PAIR_TERMS``
+    names the index of each term's unweighted value): the terms come out of the same launch, without a copy."""
+
+    def __init__(self, weight_ple=0.0, weight_rank=0.0, weight_recon=0.0, weight_mse=0.0, *, rank_gamma=1.0, rank_norm="l1",
+                 rank_add_weight=False, recon_alpha=0.0, recon_gamma=1.0, recon_norm="l1", mse_include_censored=False):
+        super().__init__()
+        if rank_add_weight:
+            raise NotImplementedError("rank_loss(add_weight=True) is not part of the launch")
+        self.weights = dict(SurvPLE=float(weight_ple), rank_loss=float(weight_rank), recon_loss=float(weight_recon), MSE_loss=float(weight_mse))
+        self.options = dict(rank_gamma=rank_gamma, rank_norm=rank_norm, recon_alpha=recon_alpha, recon_gamma=recon_gamma,
+                            recon_norm=recon_norm, mse_include_censored=mse_include_censored)
+        self._spec = _pair_spec(weight_ple, weight_rank, weight_recon, weight_mse, **self.options)
+        self.terms = None
+
+    _handler_options = {"SurvPLE": {}, "rank_loss": {"gamma": "rank_gamma", "norm": "rank_norm", "add_weight": "rank_add_weight"},
+                        "recon_loss": {"alpha": "recon_alpha", "gamma": "recon_gamma", "norm": "recon_norm"},
+                        "MSE_loss": {"include_censored": "mse_include_censored"}}
+    _handler_weight = {"SurvPLE": "weight_ple", "rank_loss": "weight_rank", "recon_loss": "weight_recon", "MSE_loss": "weight_mse"}
+
+    @classmethod
+    def from_handler(cls, loss, loss_weight, converter):
+        """The objective of a handler's ``self.loss`` (name -> ``functools.partial`` of a loss function, whose ``.keywords`` are read, or
+        a SurvPLE object: the reference's or this module's), its ``self.loss_weight`` and ``net_output_converter``.  Refuses an unknown
+        name and ``add_weight=True`` with ``NotImplementedError``, a converter other than ``None`` with ``ValueError`` (the handler's own
+        check, runner/sa_handler.py:38-40)."""
+        if converter is not None:
+            raise ValueError(f"the continuous heads need net_output_converter = None (the handler's _check_arguments), got {converter!r}")
+        kws = {}
+        for name, func in loss.items():
+            if name not in cls._handler_options:
+                raise NotImplementedError(f"{name} is not part of the launch ({', '.join(cls._handler_options)})")
+            given = getattr(func, "keywords", None) or {}
+            kws.update({mine: given[theirs] for theirs, mine in cls._handler_options[name].items() if theirs in given})
+            kws[cls._handler_weight[name]] = float(loss_weight[name])
+        return cls(**kws)
+
+    def forward(self, pred, t, e=None):
+        if e is None:
+            t, e = t[:, 0], t[:, 1]
+        return _PairFn.apply(pred, t, e, self._spec, nat.PAIR_OBJ_TOTAL)
+
+    def value_and_grad(self, pred, t, e=None):
+        """(objective, d objective / d pred in pred's shape) from the one launch, outside autograd -- for a caller that starts the
+        backward pass itself with ``pred.backward(grad)``."""
+        if e is None:
+            t, e = t[:, 0], t[:, 1]
+        self.terms, g = _pair_route(pred)(pred, t, e, self._spec)
+        return self.terms[nat.PAIR_OBJ_TOTAL], g
