@@ -97,6 +97,7 @@ int vlsa_vlfan_partial(const void* X, int x_dtype, int64_t N, int64_t ldx, int D
  * Log-sum-exp merge of G partials (from this GPU's workgroups, or all-gathered from the other ranks):
  *   m2 [16], l [16], out [P, D];  normalise != 0 -> out_p = acc_p / l_p (the reference's A @ X row),
  *   normalise == 0 -> out holds the un-normalised merged acc (a compact partial for the RCCL exchange).
+ * Any D <= 1024: a width that is no multiple of 8 (vlsa_scored_pool_partial writes such partials) is merged one column per thread.
  */
 int vlsa_vlfan_merge(const float* pm, const float* pl, const float* pacc, int G, int P, int D, int normalise,
                      float* m2, float* l, float* out, void* stream);

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void k_scored_pool_partial(const XT* __restric
             for (int i = 0; i < DPL; ++i) acc[i] *= f;
             M = t;
         }
-        const float wgt = fast_exp2(t - M);
+        const float wgt = (t == -INFINITY) ? 0.f : fast_exp2(t - M);   // (-inf before any finite score: t - M is NaN)
         l += wgt;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) acc[i] += wgt * x[i];

@@ -80,6 +80,46 @@ __global__ __launch_bounds__(256) void k_vlfan_merge(const float* __restrict__ p
     }
 }
 
+// The same merge for a width that is no multiple of 8 (the scalar pooling kernels of mil_pool.hip write such partials): one column
+// per thread instead of a float4, thread -> (column tid & 63, partial subset tid >> 6).  grid = (ceil(D/64), P) as above.
+__global__ __launch_bounds__(256) void k_vlfan_merge_cols(const float* __restrict__ pm, const float* __restrict__ pl,
+                                                           const float* __restrict__ pacc, int G, int P, int D,
+                                                           int normalise, float* __restrict__ m2, float* __restrict__ l,
+                                                           float* __restrict__ out, int64_t sm, int64_t sl_, int64_t sa) {
+    __shared__ float red[4];
+    __shared__ float sacc[4][64];
+    __shared__ float sl[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int p = blockIdx.y, col = blockIdx.x * 64 + lane;
+    const bool incol = col < D;
+    float mx = -INFINITY;
+    for (int gI = tid; gI < G; gI += 256) mx = fmaxf(mx, pm[(size_t)gI * sm + p]);
+    mx = wave_max(mx);
+    if (lane == 0) red[wv] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float a = 0.f, lt = 0.f;
+    for (int gI = wv; gI < G; gI += 4) {
+        const float mg = pm[(size_t)gI * sm + p];
+        const float f = (mg == -INFINITY) ? 0.f : fast_exp2(mg - mx);
+        lt += pl[(size_t)gI * sl_ + p] * f;
+        if (incol) a += pacc[(size_t)gI * sa + (size_t)p * D + col] * f;
+    }
+    sacc[wv][lane] = a;
+    if (lane == 0) sl[wv] = lt;
+    __syncthreads();
+    if (wv == 0) {
+        const float ls = (sl[0] + sl[1]) + (sl[2] + sl[3]);
+        float s = (sacc[0][lane] + sacc[1][lane]) + (sacc[2][lane] + sacc[3][lane]);
+        if (normalise) s *= 1.f / ls;
+        if (incol) out[(size_t)p * D + col] = s;
+        if (tid == 0 && blockIdx.x == 0) {
+            m2[p] = mx;
+            l[p] = ls;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_attn_normalise(const float* __restrict__ scores, int P, int64_t N,
                                                          const float* __restrict__ m2, const float* __restrict__ l,
                                                          float* __restrict__ A) {
@@ -700,10 +740,14 @@ extern "C" int vlsa_vlfan_merge_strided(const float* pm, int64_t pm_stride, cons
                                         const float* pacc, int64_t pacc_stride, int G, int P, int D, int normalise,
                                         float* m2, float* l, float* out, void* stream) {
     if (!pm || !pl || !pacc || !m2 || !l || !out) return VLSA_EINVAL;
-    if (G < 1 || P < 1 || P > VLSA_MAX_P || D <= 0 || D > VLSA_MAX_D || (D % 8) != 0) return VLSA_EINVAL;
-    if (pm_stride < P || pl_stride < P || pacc_stride < (int64_t)P * D || (pacc_stride % 4) != 0 ||
-        (reinterpret_cast<uintptr_t>(pacc) & 15) != 0)
-        return VLSA_EINVAL;
+    if (G < 1 || P < 1 || P > VLSA_MAX_P || D <= 0 || D > VLSA_MAX_D) return VLSA_EINVAL;
+    if (pm_stride < P || pl_stride < P || pacc_stride < (int64_t)P * D) return VLSA_EINVAL;
+    if ((D % 8) != 0) {   // the widths only vlsa_scored_pool_partial writes (P = 1, any D): one column per thread, no alignment asked
+        hipLaunchKernelGGL(k_vlfan_merge_cols, dim3((D + 63) / 64, P), dim3(256), 0, (hipStream_t)stream, pm, pl, pacc, G, P, D,
+                           normalise, m2, l, out, pm_stride, pl_stride, pacc_stride);
+        return launch_status();
+    }
+    if ((pacc_stride % 4) != 0 || (reinterpret_cast<uintptr_t>(pacc) & 15) != 0) return VLSA_EINVAL;
     hipLaunchKernelGGL(k_vlfan_merge, dim3((D + 63) / 64, P), dim3(256), 0, (hipStream_t)stream, pm, pl, pacc, G, P, D,
                        normalise, m2, l, out, pm_stride, pl_stride, pacc_stride);
     return launch_status();
