@@ -146,6 +146,9 @@ size_t vlsa_head_workspace_bytes(int D);
  *   rows [P, D]; pool_w [P] raw 'weight' pooling parameter (nullable); W [D, D], b [D] (nullable => Identity)
  *   That [K, D] UNIT-norm text features; logit_scale: device pointer to the scalar parameter (pre-exp)
  *   outputs: pooled [D], v [D], vhat [D], vnorm [1], logits [K], incidence [K] (nullable)
+ * D % 4 == 0, D <= 1024, P <= 16, K <= 64 (VLSA_EINVAL otherwise).  PRECONDITION, not checked: W is 16-byte aligned (its rows are
+ * loaded as float4) -- here and in every batched head entry below, where `pooled` must be 16-byte aligned too (the adapter kernels
+ * load it, the merge-and-pool kernel stores it as float4); likewise `out` of vlsa_vlfan_merge / vlsa_vlfan_merge_head.
  */
 int vlsa_head_forward(const float* rows, int P, int D, int pool_mode, const float* pool_w, const float* W,
                       const float* b, const float* That, int K, const float* logit_scale, void* workspace,
