@@ -569,6 +569,7 @@ int vlsa_pack_rows_bf16(const void* src, int src_dtype, int64_t N, int64_t lds, 
  * x: raw logits (from_logits = 1: the softmax converter of runner/vlsa_handler.py:245 is fused in) or incidences.
  * t: int64 bin per sample, e: 1 = event, 0 = censored.  out_ifmle / out_emd: per-sample losses [B] (either may be NULL);
  * grad [B, K] = d (w_ifmle * ifmle_i + w_emd * emd_i) / d x[i, :]  (NULL to skip).  K <= 64.
+ * A form of vlsa_surv_terms below: converter = from_logits ? VLSA_CONV_SOFTMAX : VLSA_CONV_NONE, family = VLSA_SURV_IFMLE.
  */
 int vlsa_surv_loss(const float* x, const int64_t* t, const float* e, int B, int K, int from_logits,
                    const float* logit_scale_exp, float alpha, float eps, int p, int raw_distance, float w_ifmle,
@@ -578,6 +579,7 @@ int vlsa_surv_loss(const float* x, const int64_t* t, const float* e, int B, int 
  * SurvEMD, loss/loss_surv.py:163-164, loss/loss_surv_ext.py:104-105): objective[0] = mean_i (w_ifmle * ifmle_i + w_emd * emd_i),
  * grad [B, K] = d objective / d x (NULL to skip).  logit_scale: device pointer to exp(logit_scale) as the reference's
  * net.get_logit_scale() hands it over (ls_is_log = 0), or to the raw parameter, exponentiated here (ls_is_log = 1).  B <= 4096.
+ * A form of vlsa_surv_objective_terms below: the same converter and family, w_main = w_ifmle, w_t2i = 0.
  */
 int vlsa_surv_objective(const float* x, const int64_t* t, const float* e, int B, int K, int from_logits, const float* logit_scale,
                         int ls_is_log, float alpha, float eps, int p, int raw_distance, float w_ifmle, float w_emd,
@@ -585,7 +587,7 @@ int vlsa_surv_objective(const float* x, const int64_t* t, const float* e, int B,
 
 /*
  * The handler's other objectives (runner/vlsa_handler.py:33-41: an incidence family behind the softmax, a hazard family behind the
- * sigmoid; loss/utils.py:52-76 adds SurvT2I).  The two entries above stay as they are and launch what they always launched.
+ * sigmoid; loss/utils.py:52-76 adds SurvT2I).  One kernel pair serves these and the two entries above (the same launches, the same bits).
  *
  * vlsa_surv_terms: vlsa_surv_loss with a converter code and the likelihood term named.  family = VLSA_SURV_IFMLE (SurvIFMLE,
  * loss/loss_surv.py:144-169) or VLSA_SURV_MLE (SurvMLE, loss/loss_surv.py:104-124: S_padded = [1, cumprod(1 - h)],

@@ -14,12 +14,12 @@ import surv_eval_helpers as H
 import surv_loss_cases as S
 
 # ---- what the launches branch on (tests/test_objective_cases_cpu.py::test_dispatch_constants_match_the_source reads them from the code)
-ROWS16_MAX_K = 16        # surv_objectives.hip: `if (K <= 16)` -> k_surv_terms_rows16, else k_surv_terms
+ROWS16_MAX_K = 16        # surv_objectives.hip, launch_terms: `if (a.K <= 16)` -> k_surv_terms_rows16, else k_surv_terms
 CHUNK = 32               # kTermThreads = 32 (k_surv_terms), kTermWideSamples = kTermWide / 16 = 32 (rows16): samples per pass
 T2I_GROUPS_ROWS16 = 32   # k_surv_terms_rows16: the SurvT2I column of bin k is walked by kTermWideSamples threads, thread g takes samples g, g + 32, ..
 T2I_GROUPS_WIDE = 4      # k_surv_terms: kTermBlock / kTermCols = 256 / 64 threads per column
 T2I_GROUPS_ALONE = 256   # k_t2i_columns (vlsa_surv_t2i): kT2iThreads threads per column; k_t2i_finish: as many elements per workgroup
-ONE_BLOCK_MAX_B = 4096   # vlsa_surv_objective_terms: `B > 4096` is refused; losses.py SurvObjective: `shape[0] <= 4096`
+ONE_BLOCK_MAX_B = 4096   # vlsa_surv_objective_terms: `B > kOneBlockMaxB` is refused; losses.py: ONE_LAUNCH_MAX_B
 MAX_K = S.MAX_K
 BATCH_EDGES = sorted({1, 130} | {g + d for g in (CHUNK, T2I_GROUPS_ROWS16, T2I_GROUPS_WIDE) for d in (-1, 0, 1)})
 

@@ -1,5 +1,5 @@
-"""Cases and float64 truth of the survival loss kernels (vlsa_amd/csrc/surv_loss.hip: k_surv_loss_rows16 up to 16 bins, k_surv_loss for
-17 .. 64), shared by tests/test_surv_loss_cases_cpu.py (the input conditions, the gates) and tests/test_gpu_surv_loss_edges.py (the
+"""Cases and float64 truth of the survival loss kernels on the incidence family (vlsa_amd/csrc/surv_objectives.hip: k_surv_terms_rows16 up
+to 16 bins, k_surv_terms for 17 .. 64), shared by tests/test_surv_loss_cases_cpu.py (the input conditions, the gates) and tests/test_gpu_surv_loss_edges.py (the
 kernels).  CPU only: torch and tests/surv_eval_helpers.py, whose loss formulas tests/test_surv_eval_cpu.py pins to the reference's
 float64 results."""
 import collections
@@ -11,9 +11,9 @@ import torch
 import surv_eval_helpers as H
 
 # ---- what the launches branch on
-ROWS16_MAX_K = 16        # surv_loss.hip, vlsa_surv_loss / vlsa_surv_objective: `if (K <= 16)` -> k_surv_loss_rows16, else k_surv_loss
-CHUNK = 32               # surv_loss.hip: kLossThreads = 32 (k_surv_loss), kLossWideSamples = kLossWide / 16 = 32 (rows16) samples per pass
-ONE_BLOCK_MAX_B = 4096   # surv_loss.hip, vlsa_surv_objective: `B > 4096` is refused; losses.py SurvObjective.forward: `shape[0] <= 4096`
+ROWS16_MAX_K = 16        # surv_objectives.hip, launch_terms: `if (a.K <= 16)` -> k_surv_terms_rows16, else k_surv_terms
+CHUNK = 32               # surv_objectives.hip: kTermThreads = 32 (k_surv_terms), kTermWideSamples = kTermWide / 16 = 32 (rows16) samples per pass
+ONE_BLOCK_MAX_B = 4096   # surv_objectives.hip: kOneBlockMaxB, a larger B is refused; losses.py: ONE_LAUNCH_MAX_B
 MAX_K = 64               # include/vlsa_hip.h: VLSA_MAX_K
 
 LOG_LOGIT_SCALE = 4.0309                        # the shipped checkpoint's parameter (tests/golden/cases.py LOGIT_SCALE)

@@ -29,6 +29,18 @@ def _same_bits(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
+def _direct_objective(x, t, e, ls_log, alpha, eps, p, raw, w_ifmle, w_emd):
+    """objective | gradient [1 + B K] of a direct call of vlsa_surv_objective on raw logits with the raw (log) logit scale"""
+    from vlsa_amd import _native as nat
+    B, K = x.shape
+    out = torch.full((1 + B * K,), float("nan"), device=DEV)
+    ptr = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert nat.load().vlsa_surv_objective(ptr(x), ptr(t), ptr(e), B, K, 1, ptr(ls_log), 1, alpha, eps, p, int(raw), w_ifmle, w_emd, ptr(out),
+                                          ptr(out[1:]), stream) == 0
+    return out
+
+
 def _objective(family, alpha=0.0, p=2, raw=True, w=(1.0, 1.0, 0.5), t2i_loss="CL", t2i_reduction="mean"):
     from vlsa_amd.losses import SurvObjective
     hazard = family == "hazard"
@@ -75,9 +87,10 @@ def test_objective_against_float64(c):
     i, want = C.case_inputs(c), C.case_truth(c)
     x, t, e = _dev(i.logits, i.t, i.e)
     obj = _objective(c.family, c.alpha, c.p, c.raw, (c.w_main, c.w_emd, c.w_t2i), c.t2i_loss, c.t2i_reduction)
-    if c.family == "incidence" and c.w_t2i == 0:
-        assert obj._default         # nothing new asked: the launch of before
-    _check_routes(c.name, c.family, obj, x, t, e, want, c.B)
+    got, grad = _check_routes(c.name, c.family, obj, x, t, e, want, c.B)
+    if c.family == "incidence" and c.w_t2i == 0 and c.B <= C.ONE_BLOCK_MAX_B:      # nothing new asked: the bits of vlsa_surv_objective
+        out = _direct_objective(x, t, e, torch.tensor(C.LOG_LOGIT_SCALE, device=DEV), c.alpha, C.EPS, c.p, c.raw, c.w_main, c.w_emd)
+        assert _same_bits(got, out[0]) and _same_bits(grad, out[1:].view(c.B, c.K))
 
 
 @pytest.mark.parametrize("c", C.FIXTURES, ids=C.ids(C.FIXTURES))
@@ -199,24 +212,53 @@ def test_two_runs_give_the_same_bits(family, K, B):
 # ---- 4. the default route is the launch it was
 @pytest.mark.parametrize("K,B", [(12, 32), (17, 33)])
 def test_default_objective_is_the_direct_call_of_vlsa_surv_objective(K, B):
-    from vlsa_amd import _native as nat
     from vlsa_amd.losses import SurvObjective
     i = S.make_inputs(B, K, 5000 + 100 * K + B, 2.0)
     x, t, e = _dev(i.logits, i.t, i.e)
     ls_log = torch.tensor(C.LOG_LOGIT_SCALE, device=DEV)
-    lib = nat.load()
-    out = torch.full((1 + B * K,), float("nan"), device=DEV)
-    p = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert lib.vlsa_surv_objective(p(x), p(t), p(e), B, K, 1, p(ls_log), 1, 0.0, 1e-7, 2, 1, 1.0, 1.0, p(out), p(out[1:]), stream) == 0
+    out = _direct_objective(x, t, e, ls_log, 0.0, 1e-7, 2, True, 1.0, 1.0)
     obj = SurvObjective()
-    assert obj._default
     xd = x.clone().requires_grad_(True)
     got = obj(xd, t, e, log_logit_scale=ls_log)
     got.backward()
     assert torch.equal(got.detach(), out[0]) and torch.equal(xd.grad, out[1:].view(B, K))
     v, g = obj.value_and_grad(x, t, e, log_logit_scale=ls_log)
     assert torch.equal(v, out[0]) and torch.equal(g, out[1:].view(B, K))
+
+
+@pytest.mark.parametrize("K", [12, 17])        # one per kernel; 33 samples: a full chunk plus one
+def test_the_first_entry_points_forward_to_the_terms_launches(K):
+    """vlsa_surv_loss and vlsa_surv_objective are forms of vlsa_surv_terms and vlsa_surv_objective_terms: the same bits"""
+    from vlsa_amd import _native as nat
+    B = 33
+    i = S.make_inputs(B, K, 5000 + 100 * K + B, 2.0)
+    x, t, e = _dev(i.logits, i.t, i.e)
+    inc = torch.softmax(x, dim=-1)
+    ls, ls_log = torch.tensor(C.LOGIT_SCALE, device=DEV), torch.tensor(C.LOG_LOGIT_SCALE, device=DEV)
+    lib = nat.load()
+    ptr = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    alpha, eps, p, raw, w1, w2 = 0.3, C.EPS, 2, 0, 0.7, 1.3
+
+    def rows(call):
+        o1, o2, g = torch.full((B,), float("nan"), device=DEV), torch.full((B,), float("nan"), device=DEV), torch.full((B, K), float("nan"), device=DEV)
+        assert call(o1, o2, g) == 0
+        assert bool(torch.isfinite(o1).all()) and bool(torch.isfinite(o2).all()) and bool(torch.isfinite(g).all())
+        return o1, o2, g
+
+    for pred, from_logits, conv in ((inc, 0, nat.CONV_NONE), (x, 1, nat.CONV_SOFTMAX)):
+        old = rows(lambda o1, o2, g: lib.vlsa_surv_loss(ptr(pred), ptr(t), ptr(e), B, K, from_logits, ptr(ls), alpha, eps, p, raw, w1, w2, ptr(o1),
+                                                        ptr(o2), ptr(g), stream))
+        new = rows(lambda o1, o2, g: lib.vlsa_surv_terms(ptr(pred), ptr(t), ptr(e), B, K, conv, nat.SURV_IFMLE, ptr(ls), alpha, eps, p, raw, w1, w2,
+                                                         ptr(o1), ptr(o2), ptr(g), stream))
+        assert all(_same_bits(a, b) for a, b in zip(old, new)), from_logits
+    for scale, is_log in ((ls, 0), (ls_log, 1)):
+        old, new = (torch.full((1 + B * K,), float("nan"), device=DEV) for _ in range(2))
+        assert lib.vlsa_surv_objective(ptr(x), ptr(t), ptr(e), B, K, 1, ptr(scale), is_log, alpha, eps, p, raw, w1, w2, ptr(old), ptr(old[1:]),
+                                       stream) == 0
+        assert lib.vlsa_surv_objective_terms(ptr(x), ptr(t), ptr(e), B, K, nat.CONV_SOFTMAX, nat.SURV_IFMLE, ptr(scale), is_log, alpha, eps, p, raw,
+                                             w1, w2, 0.0, nat.T2I_CL, nat.T2I_MEAN, ptr(new), ptr(new[1:]), stream) == 0
+        assert bool(torch.isfinite(old).all()) and _same_bits(old, new), is_log
 
 
 # ---- 5. the entries refuse bad arguments before any launch (real buffers large enough for every variant, should one slip through)

@@ -1,5 +1,5 @@
-"""The survival loss kernels (vlsa_amd/csrc/surv_loss.hip) at every bin count and batch size their launches branch on -- the DPP kernel
-k_surv_loss_rows16 up to 16 bins, the one-thread-per-sample kernel k_surv_loss for 17 .. 64, each as one block per 32 samples
+"""The survival loss kernels (vlsa_amd/csrc/surv_objectives.hip) on the incidence family, at every bin count and batch size their launches
+branch on -- the DPP kernel k_surv_terms_rows16 up to 16 bins, the one-thread-per-sample kernel k_surv_terms for 17 .. 64, each as one block per 32 samples
 (vlsa_surv_loss) and as one block walking the batch (vlsa_surv_objective) -- against the float64 truth of tests/surv_loss_cases.py.
 The gates are 8 x what a plain fp32 evaluation of the same formulas reaches (tests/test_surv_loss_cases_cpu.py measures them); gradients
 are held relative to the largest entry of the float64 gradient.  Every comparison prints its measured error next to the gate."""
@@ -148,7 +148,7 @@ def test_labels_out_of_range_are_clamped(K):
         assert _same_bits(res[0][0], res[1][0]) and _same_bits(res[0][1], res[1][1]), which
 
 
-# ---- 5. the two kernels on the same problem: 12 bins (rows16), and the same 12 bins zero-padded to 17 (k_surv_loss)
+# ---- 5. the two kernels on the same problem: 12 bins (rows16), and the same 12 bins zero-padded to 17 (k_surv_terms)
 def test_rows16_and_the_per_thread_kernel_agree_on_a_padded_problem():
     from vlsa_amd.losses import SurvIFMLE
     i = C.make_inputs(33, 12, 7500, 2.0)
@@ -165,7 +165,7 @@ def test_rows16_and_the_per_thread_kernel_agree_on_a_padded_problem():
     bit_equal = _same_bits(v12, v17) and _same_bits(g12, g17[:, :12].contiguous())
     dv = float(((v12 - v17).abs() / v12.abs()).max())
     dg = C.rel_grad_rows(g17[:, :12], g12)
-    print(f"K = 12 (rows16) vs zero-padded K = 17 (k_surv_loss): values {dv:.2e} gradient rows {dg:.2e} (gate 1e-06); bit-equal: {bit_equal}")
+    print(f"K = 12 (rows16) vs zero-padded K = 17 (k_surv_terms): values {dv:.2e} gradient rows {dg:.2e} (gate 1e-06); bit-equal: {bit_equal}")
     assert dv <= 1e-6 and dg <= 1e-6
     assert bool((g17[:, 12:] == 0).all())           # the padding bins lie beyond every label
 

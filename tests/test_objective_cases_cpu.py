@@ -25,12 +25,14 @@ def test_dispatch_constants_match_the_source():
     def const(name):
         return int(re.search(rf"\b{name} = (\d+)\b", src).group(1))
 
-    assert C.MAX_K == nat.MAX_K and C.ROWS16_MAX_K < C.MAX_K and src.count("if (K <= 16)") == 2 and C.ROWS16_MAX_K == 16
+    assert C.MAX_K == nat.MAX_K and C.ROWS16_MAX_K < C.MAX_K and src.count("if (a.K <= 16)") == 1 and C.ROWS16_MAX_K == 16
     assert C.CHUNK == const("kTermThreads") == const("kTermWide") // 16 and "kTermWideSamples = kTermWide / 16" in src
     assert C.T2I_GROUPS_ROWS16 == const("kTermWide") // 16
     assert C.T2I_GROUPS_WIDE == const("kTermBlock") // const("kTermCols") and const("kTermCols") == nat.MAX_K
     assert C.T2I_GROUPS_ALONE == const("kT2iThreads")
-    assert src.count("B > 4096") == 1 and C.ONE_BLOCK_MAX_B == 4096
+    assert src.count("B > kOneBlockMaxB") == 2 and C.ONE_BLOCK_MAX_B == S.ONE_BLOCK_MAX_B == const("kOneBlockMaxB") == 4096
+    from vlsa_amd import losses
+    assert losses.ONE_LAUNCH_MAX_B == C.ONE_BLOCK_MAX_B
     assert nat.EVAL_MAX_M == 65536 and "B > VLSA_EVAL_MAX_M" in src
 
 
@@ -279,8 +281,10 @@ class _Loss:
 def test_objective_construction_and_refusals():
     from vlsa_amd import SurvObjective, _native as nat
     o = SurvObjective()
-    assert o._default and (o.converter, o.w_mle, o.w_t2i, o.t2i_loss, o.t2i_reduction) == ("softmax", 0.0, 0.0, "CL", "mean")
-    assert SurvObjective(0.5, 2.0, 0.3, 1e-6, 1, False)._default                     # the positional arguments are the old ones
+    assert (o.converter, o.w_mle, o.w_t2i, o.t2i_loss, o.t2i_reduction) == ("softmax", 0.0, 0.0, "CL", "mean")
+    assert o._spec() == (nat.CONV_SOFTMAX, nat.SURV_IFMLE, 0.0, 1e-7, 2, True, 1.0, 1.0, 0.0, "CL", "mean")
+    # the positional arguments are the old ones
+    assert SurvObjective(0.5, 2.0, 0.3, 1e-6, 1, False)._spec() == (nat.CONV_SOFTMAX, nat.SURV_IFMLE, 0.3, 1e-6, 1, False, 0.5, 2.0, 0.0, "CL", "mean")
     with pytest.raises(TypeError):
         SurvObjective(1.0, 1.0, 0.0, 1e-7, 2, True, "sigmoid")                      # the new ones are keyword-only
     with pytest.raises(ValueError, match="softmax"):
@@ -294,10 +298,9 @@ def test_objective_construction_and_refusals():
     with pytest.raises(NotImplementedError):
         SurvObjective(p=3)
     o = SurvObjective(weight_ifmle=0, weight_mle=1, weight_emd=1, weight_t2i=0.5, converter="sigmoid")
-    assert not o._default
     assert o._spec() == (nat.CONV_SIGMOID, nat.SURV_MLE, 0.0, 1e-7, 2, True, 1, 1, 0.5, "CL", "mean")
     o = SurvObjective(weight_t2i=0.25, t2i_loss="KL", t2i_reduction="sum")
-    assert not o._default and o._spec()[:2] == (nat.CONV_SOFTMAX, nat.SURV_IFMLE) and o._spec()[-3:] == (0.25, "KL", "sum")
+    assert o._spec()[:2] == (nat.CONV_SOFTMAX, nat.SURV_IFMLE) and o._spec()[-3:] == (0.25, "KL", "sum")
 
 
 def test_from_handler_reads_either_code_bases_objects():
@@ -311,7 +314,7 @@ def test_from_handler_reads_either_code_bases_objects():
         assert o._spec() == (nat.CONV_SIGMOID, nat.SURV_MLE, 0.3, 1e-6, 1, True, 1.0, 0.7, 0.2, "KL", "sum")
     o = SurvObjective.from_handler({"SurvIFMLE": _Loss(alpha=0.0, eps=1e-7, reduction="mean"), "SurvEMD": _Loss(p=2, raw_distance=False, reduction="mean")},
                                    {"SurvIFMLE": 1.0, "SurvEMD": 1.0}, "softmax")
-    assert o._default and (o.w1, o.w2, o.p, o.raw) == (1.0, 1.0, 2, False)
+    assert o._spec() == (nat.CONV_SOFTMAX, nat.SURV_IFMLE, 0.0, 1e-7, 2, False, 1.0, 1.0, 0.0, "CL", "mean")
     with pytest.raises(ValueError):         # the handler's rule
         SurvObjective.from_handler({"SurvMLE": _Loss(alpha=0.0, eps=1e-7)}, {"SurvMLE": 1.0}, "softmax")
     for bad in ({"QueryDiv": _Loss()}, {"SurvEMD": _Loss(p=3, raw_distance=True, reduction="mean")},

@@ -13,7 +13,7 @@ rows = []
 for r in csv.DictReader(open(t)):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
 rows.sort()
-idx = [i for i, r in enumerate(rows) if "k_surv_loss" in r[2]]
+idx = [i for i, r in enumerate(rows) if "k_surv_terms" in r[2]]
 a, b = idx[-12], idx[-2]
 seg, n = rows[a:b], 10
 tot = (seg[-1][0] - seg[0][0]) / 1e3 / n

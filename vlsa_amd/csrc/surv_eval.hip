@@ -12,7 +12,7 @@ namespace vlsa {
 // ---- per-sample work: one thread per sample, ONE workgroup walking the samples in chunks of blockDim.x, so that every sum has one
 // fixed order (thread-local over the chunks, then the lanes of a wave, then the waves) and two runs give the same bits.  The sample's
 // converted prediction (K doubles) lives in LDS, [k][thread]: as a dynamically indexed private array it would sit in scratch memory
-// (see k_surv_loss).  The launch sizes the workgroup so that K * blockDim.x doubles fit kEvalLdsDoubles.
+// (see k_surv_terms).  The launch sizes the workgroup so that K * blockDim.x doubles fit kEvalLdsDoubles.
 constexpr int kEvalLdsDoubles = 7680;       // 60 KB
 constexpr int kEvalMaxThreads = 256;
 constexpr int kEvalSums = 6;                // result[0 .. 5]
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kEvalMaxThreads) void k_surv_eval_rows(
         acc[1] += (1.0 - 0.0) * (cen + unc) + 0.0 * unc;    // loss_mle_org: the same expression at alpha = 0 (an infinite unc gives the reference's NaN)
         acc[4] += e != 0.0 ? 1.0 : 0.0;
         acc[5] += (est - est == 0.0) ? 0.0 : 1.0;          // inf - inf and NaN - NaN are NaN
-        // ---- ext losses of the handler (incidence only): SurvIFMLE with its own alpha / eps, SurvEMD as in k_surv_loss
+        // ---- ext losses of the handler (incidence only): SurvIFMLE with its own alpha / eps, SurvEMD as in k_surv_terms
         if (ext_mask & 1) {
             const double u = -(1.0 - c) * log(clamp_min(a, ext_eps)), z = -c * log(clamp_min(s_at, ext_eps));
             acc[2] += (1.0 - ext_alpha) * (z + u) + ext_alpha * u;

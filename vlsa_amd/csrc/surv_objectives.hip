@@ -1,9 +1,11 @@
-// The handler's other objectives on the device (runner/vlsa_handler.py:33-41, 241-258; loss/utils.py:52-76): the HAZARD family -- SurvMLE
-// (loss/loss_surv.py:89-124) behind the sigmoid converter, with SurvEMD on the hazards -- next to the incidence family of surv_loss.hip,
-// and SurvT2I (loss/loss_surv_ext.py:126-195), a masked softmax over the SAMPLES of the batch for each time bin.  Same structure as
-// surv_loss.hip: a 16-lane row per sample up to 16 bins, a sample per thread with LDS vectors up to 64; cumulative products and sums in
-// bin order (see row16_prefix); every reduction in a fixed order: two runs give the same bits.  surv_loss.hip's kernels stay as they are:
-// the SurvEMD block is repeated here.
+// On-device loss tail of the training step: the handler's objectives on the [B, K] bag predictions
+// (runner/vlsa_handler.py:33-41, 241-258; loss/utils.py:52-76), forward AND gradient in one launch, from the raw logits (the handler's
+// converter fused in) or from converted values.  The INCIDENCE family -- SurvIFMLE (loss/loss_surv.py:127-169) behind the softmax -- and
+// the HAZARD family -- SurvMLE (loss/loss_surv.py:89-124) behind the sigmoid --, each with SurvEMD (loss/loss_surv_ext.py:43-109,
+// cdf_loss 13-38) on the converted values, and SurvT2I (loss/loss_surv_ext.py:126-195), a masked softmax over the SAMPLES of the batch
+// for each time bin.  The reference spends ~40 elementwise launches and a Python loop over the batch (convert_survival_label) on this.
+// One kernel pair serves every entry point: a 16-lane row per sample up to 16 bins, a sample per thread with LDS vectors up to 64;
+// cumulative products and sums in bin order (see row16_prefix); every reduction in a fixed order: two runs give the same bits.
 #include "vlsa_common.h"
 #include "launch.h"
 #include "surv_rows16.h"
@@ -108,25 +110,38 @@ __device__ __forceinline__ void t2i_total(const T2iCol* cols, const double* val,
 }
 
 // ---- 17 .. 64 bins: one sample per thread (the first kTermThreads threads of the block), the K-vectors in LDS [vector][k][thread].
-// objective != null: ONE block of kTermBlock threads; all of them take the SurvT2I columns (a bin per thread, kTermBlock / 64 sample groups).
+// (As dynamically indexed private arrays the K-vectors sat in scratch memory and the launch took 18.6 us for 32 samples x 12 bins, round 4:
+// profiles/r04_step_kernel_stats.csv.  Same serial order per sample as then: the results are bit-identical.)
+// objective == null: a block of kTermThreads per 32 samples, per-sample values and the unscaled gradient rows.
+// objective != null (round 6): ONE block of kTermBlock threads; its first 32 walk the batch in chunks of 32 samples and also write the scalar
+// objective[0] = mean_i (w_main main_i + w_emd emd_i) (+ w_t2i T2I) -- the handler's calc_objective_loss for 'mean'-reduced losses -- and
+// `grad` comes out scaled by 1 / B (the gradient of that mean): the five elementwise / reduction launches behind the per-sample values
+// were 25 us of a 1.7 ms optimizer step.  ls_is_log: `ls` points at the RAW (log) logit scale parameter and is exponentiated here (saves
+// the step's `logit_scale.exp()` launch).  All kTermBlock threads take the SurvT2I columns (a bin per thread, kTermBlock / 64 sample groups).
+// (Round 6, tried and removed: the same arithmetic with the per-sample vectors in registers and every bin loop unrolled to 16 -- 14.1 us
+//  against 12.5 us for the LDS loops below inside the training step: one wave running ~20 KB of straight-line code once is bound by
+//  instruction fetch, not by the LDS round trips.  Parking the sample's K inputs in LDS with one batch of loads first: no change either,
+//  12.7 -> 13.5 us on another box -- the time is the ~500 dependent LDS accesses of the bin loops.)
 constexpr int kTermThreads = 32, kTermBlock = 256, kTermCols = 64;
 struct TermVec {
     float* p;
     __device__ __forceinline__ float& operator[](int k) const { return p[k * kTermThreads]; }
 };
+template <bool T2I>
 __global__ __launch_bounds__(kTermBlock) void k_surv_terms(const SurvTermArgs a) {
     __shared__ float sm[4][VLSA_MAX_K][kTermThreads];
     __shared__ T2iScratch<kTermBlock> sc;
     __shared__ T2iCol cols[kTermCols];
     __shared__ double colval[kTermCols];
     const int tid = threadIdx.x, B = a.B, K = a.K;
-    const bool obj = a.objective != nullptr, t2i = obj && a.w_t2i != 0.f;
+    constexpr bool t2i = T2I;
+    const bool obj = a.objective != nullptr;
     const bool need_emd = a.w_emd != 0.f || a.out_emd != nullptr;
     float ls = 0.f;
     if (need_emd || t2i) ls = a.ls_is_log ? expf(a.ls[0]) : a.ls[0];
     double t2i_value = 0.;
     float t2i_coef = 0.f;
-    if (t2i) {
+    if constexpr (t2i) {
         t2i_column<kTermBlock>(a.x, a.t, a.e, B, K, tid % kTermCols, tid % kTermCols, kTermCols, tid / kTermCols, kTermBlock / kTermCols, ls, a.t2i_kl,
                                sc, cols, colval);
         t2i_total(cols, colval, K, a.t2i_mean, a.w_t2i, t2i_value, t2i_coef);
@@ -181,7 +196,7 @@ __global__ __launch_bounds__(kTermBlock) void k_surv_terms(const SurvTermArgs a)
             if (st1 >= eps) cLE = w_main * (1.f - alpha) * c;
         }
 
-        // ---- SurvEMD on y (surv_loss.hip's block)
+        // ---- SurvEMD on y
         float l_emd = 0.f, emd_outer = 0.f, emd_dot = 0.f;
         if (need_emd) {
             float mp = -INFINITY, mt = -INFINITY;
@@ -241,7 +256,9 @@ __global__ __launch_bounds__(kTermBlock) void k_surv_terms(const SurvTermArgs a)
                 float g = pd[k];
                 if (a.conv == VLSA_CONV_SOFTMAX) g = y[k] * (g - ydot);      // softmax backward to the raw logits
                 g *= gscale;
-                if (t2i) g += t2i_coef * t2i_grad(xi[k], ei != 0, t, k, cols[k]);
+                // (an explicit fma onto the ROUNDED g * gscale, as the kernel computed it while SurvT2I was a run-time branch: left to the
+                //  compiler, the product g * gscale is the one that gets fused into the sum -- another last bit)
+                if constexpr (t2i) g = fmaf(t2i_coef, t2i_grad(xi[k], ei != 0, t, k, cols[k]), g);
                 gi[k] = g;
             }
         }
@@ -254,16 +271,23 @@ __global__ __launch_bounds__(kTermBlock) void k_surv_terms(const SurvTermArgs a)
     }
 }
 
-// ---- K <= 16 bins: a sample per 16-lane row, a bin per lane, 32 samples per 512-thread workgroup and pass (k_surv_loss_rows16's layout);
-// the SurvT2I columns: bin = lane of the row, 32 sample groups.
+// ---- K <= 16 bins (the reference's 4 .. 12): a sample per 16-LANE ROW, a bin per lane -- every loop over the bins above becomes a row
+// operation through DPP (sum / max by row rotations, the cumulative sums and products by shifted adds and multiplies), 32 samples per
+// 512-thread workgroup and pass.  Same formulas; the cumulative sums keep the bin order (see row16_prefix), plain sums run in tree order.
+// Inside the training step, SurvIFMLE + SurvEMD: 12.7 -> 4.7 us = the floor of a launch (the loops above are ~500 dependent LDS accesses
+// on one wave; measured on k_surv_loss_rows16, the kernel this one took over: back to back the same work is 3.55 us here against 3.44 us
+// there, profiles/r22_surv_terms_fold_ab.txt).  (row16_sum: vlsa_common.h; row16_max, row16_prefix, row16_suffix, row16_prefix_prod: surv_rows16.h)
+// The SurvT2I columns: bin = lane of the row, 32 sample groups.
 constexpr int kTermWide = 512, kTermWideSamples = kTermWide / 16;
+template <bool T2I>
 __global__ __launch_bounds__(kTermWide) void k_surv_terms_rows16(const SurvTermArgs a) {
     __shared__ float sval[kTermWideSamples];
     __shared__ T2iScratch<kTermWide> sc;
     __shared__ T2iCol cols[16];
     __shared__ double colval[16];
     const int tid = threadIdx.x, k = tid & 15, sub = tid >> 4, B = a.B, K = a.K;
-    const bool obj = a.objective != nullptr, kk = k < K, t2i = obj && a.w_t2i != 0.f;
+    constexpr bool t2i = T2I;
+    const bool obj = a.objective != nullptr, kk = k < K;
     const bool need_emd = a.w_emd != 0.f || a.out_emd != nullptr;
     const int n_chunks = obj ? (B + kTermWideSamples - 1) / kTermWideSamples : 1;
     const float gscale = obj ? 1.f / (float)B : 1.f;
@@ -274,7 +298,7 @@ __global__ __launch_bounds__(kTermWide) void k_surv_terms_rows16(const SurvTermA
     double t2i_value = 0.;
     float t2i_coef = 0.f;
     T2iCol col{0.f, 0.f, 0.f, 0.f};
-    if (t2i) {
+    if constexpr (t2i) {
         t2i_column<kTermWide>(a.x, a.t, a.e, B, K, k, k, 16, sub, kTermWideSamples, ls, a.t2i_kl, sc, cols, colval);
         t2i_total(cols, colval, K, a.t2i_mean, a.w_t2i, t2i_value, t2i_coef);
         if (kk) col = cols[k];
@@ -356,7 +380,7 @@ __global__ __launch_bounds__(kTermWide) void k_surv_terms_rows16(const SurvTermA
             const float ydot = row16_sum(y * g);
             if (a.conv == VLSA_CONV_SOFTMAX) g = y * (g - ydot);          // softmax backward to the raw logits
             g *= gscale;
-            if (t2i && kk) g += t2i_coef * t2i_grad(xv, ei != 0, t, k, col);
+            if constexpr (t2i) { if (kk) g += t2i_coef * t2i_grad(xv, ei != 0, t, k, col); }
             if (valid && kk) a.grad[(size_t)i * K + k] = g;
         }
         if (obj) {
@@ -415,6 +439,8 @@ __global__ __launch_bounds__(kT2iThreads) void k_t2i_finish(const float* __restr
 
 using namespace vlsa;
 
+constexpr int kOneBlockMaxB = 4096;       // one block walks the batch
+
 static int check_terms(const float* x, const int64_t* t, const float* e, int B, int K, int conv, int family, const float* ls, float w_emd,
                        bool want_emd, int p) {
     if (!x || !t || !e || B < 1 || K < 1 || K > VLSA_MAX_K) return VLSA_EINVAL;
@@ -427,18 +453,27 @@ static int check_terms(const float* x, const int64_t* t, const float* e, int B, 
     return VLSA_OK;
 }
 
+// The dispatch of every entry point below.  a.objective == null: a block per 32 samples; else the ONE block that walks the batch.
+// SurvT2I is a compile-time parameter of both kernels: the instantiation without it carries neither the column scratch nor its registers,
+// and above 16 bins it is launched without the threads that would only walk the columns.
+static int launch_terms(const SurvTermArgs& a, void* stream) {
+    const bool obj = a.objective != nullptr, t2i = obj && a.w_t2i != 0.f;
+    if (a.K <= 16)
+        hipLaunchKernelGGL(t2i ? k_surv_terms_rows16<true> : k_surv_terms_rows16<false>,
+                           dim3(obj ? 1 : (a.B + kTermWideSamples - 1) / kTermWideSamples), dim3(kTermWide), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(t2i ? k_surv_terms<true> : k_surv_terms<false>, dim3(obj ? 1 : (a.B + kTermThreads - 1) / kTermThreads),
+                           dim3(t2i ? kTermBlock : kTermThreads), 0, (hipStream_t)stream, a);
+    return launch_status();
+}
+
 extern "C" int vlsa_surv_terms(const float* x, const int64_t* t, const float* e, int B, int K, int converter, int family,
                                const float* logit_scale_exp, float alpha, float eps, int p, int raw_distance, float w_main, float w_emd,
                                float* out_main, float* out_emd, float* grad, void* stream) {
     const int rc = check_terms(x, t, e, B, K, converter, family, logit_scale_exp, w_emd, out_emd != nullptr, p);
     if (rc != VLSA_OK) return rc;
-    const SurvTermArgs a{x, t, e, B, K, converter, family, logit_scale_exp, 0, alpha, eps, p, raw_distance, w_main, w_emd, 0.f, 0, 0,
-                         out_main, out_emd, grad, nullptr};
-    if (K <= 16)
-        hipLaunchKernelGGL(k_surv_terms_rows16, dim3((B + kTermWideSamples - 1) / kTermWideSamples), dim3(kTermWide), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_surv_terms, dim3((B + kTermThreads - 1) / kTermThreads), dim3(kTermThreads), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_terms(SurvTermArgs{x, t, e, B, K, converter, family, logit_scale_exp, 0, alpha, eps, p, raw_distance, w_main, w_emd, 0.f, 0, 0,
+                                     out_main, out_emd, grad, nullptr}, stream);
 }
 
 extern "C" int vlsa_surv_objective_terms(const float* x, const int64_t* t, const float* e, int B, int K, int converter, int family,
@@ -447,19 +482,32 @@ extern "C" int vlsa_surv_objective_terms(const float* x, const int64_t* t, const
                                          float* grad, void* stream) {
     const int rc = check_terms(x, t, e, B, K, converter, family, logit_scale, w_emd, false, p);
     if (rc != VLSA_OK) return rc;
-    if (!objective || B > 4096) return VLSA_EINVAL;
+    if (!objective || B > kOneBlockMaxB) return VLSA_EINVAL;
     if (w_t2i != 0.f) {
         if (converter == VLSA_CONV_NONE || !logit_scale) return VLSA_EINVAL;       // SurvT2I reads the raw logits
         if ((t2i_loss != VLSA_T2I_CL && t2i_loss != VLSA_T2I_KL) || (t2i_reduction != VLSA_T2I_SUM && t2i_reduction != VLSA_T2I_MEAN))
             return VLSA_EUNSUPPORTED;
     }
-    const SurvTermArgs a{x, t, e, B, K, converter, family, logit_scale, ls_is_log, alpha, eps, p, raw_distance, w_main, w_emd, w_t2i,
-                         t2i_loss == VLSA_T2I_KL, t2i_reduction == VLSA_T2I_MEAN, nullptr, nullptr, grad, objective};
-    if (K <= 16)
-        hipLaunchKernelGGL(k_surv_terms_rows16, dim3(1), dim3(kTermWide), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_surv_terms, dim3(1), dim3(kTermBlock), 0, (hipStream_t)stream, a);
-    return launch_status();
+    return launch_terms(SurvTermArgs{x, t, e, B, K, converter, family, logit_scale, ls_is_log, alpha, eps, p, raw_distance, w_main, w_emd, w_t2i,
+                                     t2i_loss == VLSA_T2I_KL, t2i_reduction == VLSA_T2I_MEAN, nullptr, nullptr, grad, objective}, stream);
+}
+
+// ---- the incidence family under its first names: SurvIFMLE + SurvEMD from the raw logits (from_logits != 0: the softmax converter) or
+// from incidences.  vlsa_surv_loss is vlsa_surv_terms, vlsa_surv_objective is vlsa_surv_objective_terms without SurvT2I.
+extern "C" int vlsa_surv_loss(const float* x, const int64_t* t, const float* e, int B, int K, int from_logits,
+                              const float* logit_scale_exp, float alpha, float eps, int p, int raw_distance, float w_ifmle,
+                              float w_emd, float* out_ifmle, float* out_emd, float* grad, void* stream) {
+    return vlsa_surv_terms(x, t, e, B, K, from_logits ? VLSA_CONV_SOFTMAX : VLSA_CONV_NONE, VLSA_SURV_IFMLE, logit_scale_exp, alpha, eps, p,
+                           raw_distance, w_ifmle, w_emd, out_ifmle, out_emd, grad, stream);
+}
+
+// logit_scale: the EXPONENTIATED scale (ls_is_log == 0, the reference's `net.get_logit_scale()`) or the raw parameter (ls_is_log != 0).
+extern "C" int vlsa_surv_objective(const float* x, const int64_t* t, const float* e, int B, int K, int from_logits, const float* logit_scale,
+                                   int ls_is_log, float alpha, float eps, int p, int raw_distance, float w_ifmle, float w_emd,
+                                   float* objective, float* grad, void* stream) {
+    if (!objective || B > kOneBlockMaxB) return VLSA_EINVAL;                       // (ahead of the check of p, as this entry always had it)
+    return vlsa_surv_objective_terms(x, t, e, B, K, from_logits ? VLSA_CONV_SOFTMAX : VLSA_CONV_NONE, VLSA_SURV_IFMLE, logit_scale, ls_is_log,
+                                     alpha, eps, p, raw_distance, w_ifmle, w_emd, 0.f, VLSA_T2I_CL, VLSA_T2I_MEAN, objective, grad, stream);
 }
 
 extern "C" int vlsa_surv_t2i(const float* x, const int64_t* t, const float* e, int B, int K, const float* logit_scale, int ls_is_log,

@@ -1,4 +1,4 @@
-// Row operations of the survival loss kernels (surv_loss.hip, surv_objectives.hip): a sample per 16-LANE ROW, a bin per lane, through DPP.
+// Row operations of the survival loss kernels (surv_objectives.hip): a sample per 16-LANE ROW, a bin per lane, through DPP.
 #pragma once
 #include "vlsa_common.h"
 

@@ -1,13 +1,13 @@
-"""Loss tail of the training step on the device: ``SurvIFMLE`` (loss/loss_surv.py:127-169) and ``SurvEMD``
-(loss/loss_surv_ext.py:58-109) with the reference's constructor arguments and call signatures, plus ``SurvObjective`` =
-the handler's ``calc_objective_loss`` for ``loss_type: SurvIFMLE-SurvEMD`` (runner/vlsa_handler.py:241-258) taking the RAW
-bag logits (softmax converter fused in).  Forward value and gradient come from ONE kernel launch (``vlsa_surv_loss``);
-autograd only scales the saved gradient by the incoming one.
+"""Loss tail of the training step on the device, from the launches of ``csrc/surv_objectives.hip``: the handler's
+[B, K] losses (runner/vlsa_handler.py:33-41, loss/utils.py:52-76) with the reference's constructor arguments and call signatures --
+``SurvIFMLE`` (loss/loss_surv.py:127-169) on incidences, ``SurvMLE`` (loss/loss_surv.py:89-124) on hazards, ``SurvEMD``
+(loss/loss_surv_ext.py:58-109) on either, ``SurvT2I`` (loss/loss_surv_ext.py:126-195) on the raw logits -- plus ``SurvObjective`` = the
+handler's ``calc_objective_loss`` (runner/vlsa_handler.py:241-258) taking the RAW bag logits (softmax or sigmoid converter fused in).
 
-The handler's other objectives (runner/vlsa_handler.py:33-41, loss/utils.py:52-76) come from the launches of
-``csrc/surv_objectives.hip``: the hazard family -- ``SurvMLE`` (loss/loss_surv.py:89-124) behind the sigmoid converter, ``SurvEMD`` on
-the hazards -- and ``SurvT2I`` (loss/loss_surv_ext.py:126-195).  ``SurvObjective(converter=..., weight_mle=..., weight_t2i=...)`` takes
-them in one launch too; with its defaults it issues exactly the launch it always issued.
+Every module goes the same way: one preparation of the tensors (``_prep``, ``_scale``), a launch that returns the value AND its gradient
+(``_launch_terms``: per-sample values and gradient rows, any batch; ``_launch_objective_terms``: the whole 'mean'-reduced objective in ONE
+launch, up to ``ONE_LAUNCH_MAX_B`` samples), and one autograd function (``_LaunchFn``) that only scales the saved gradient by the
+incoming one.
 
 The continuous heads of runner/sa_handler.py -- ``SurvPLE`` (loss/loss_surv.py:172-209), ``rank_loss``, ``recon_loss`` and ``MSE_loss``
 (lines 11-86) on a one-column prediction -- come from the launch of ``csrc/surv_pairs.hip``; ``SurvPairObjective`` is their
@@ -23,74 +23,9 @@ from . import _native as nat
 from .functional import _need_gpu, _p, _stream
 
 
-def _launch(x, t, e, from_logits, ls, alpha, eps, p, raw, w_ifmle, w_emd, want_grad):
-    _need_gpu(x)
-    lib = nat.load()
-    x = x.detach().float().contiguous()
-    B, K = x.shape
-    t = t.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
-    e = e.reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
-    if t.numel() != B or e.numel() != B:
-        raise ValueError("t and e must hold one entry per sample")
-    if ls is not None and not isinstance(ls, torch.Tensor):
-        ls = torch.tensor(float(ls), device=x.device)
-    if ls is not None:
-        ls = ls.detach().to(device=x.device, dtype=torch.float32).reshape(1).contiguous()
-    o1 = torch.empty(B, dtype=torch.float32, device=x.device) if w_ifmle != 0 else None
-    o2 = torch.empty(B, dtype=torch.float32, device=x.device) if w_emd != 0 else None
-    g = torch.empty(B, K, dtype=torch.float32, device=x.device) if want_grad else None
-    nat.check(lib.vlsa_surv_loss(_p(x), _p(t), _p(e), B, K, int(from_logits), _p(ls), float(alpha), float(eps), int(p),
-                                 int(raw), float(w_ifmle), float(w_emd), _p(o1), _p(o2), _p(g), _stream()), "vlsa_surv_loss")
-    return o1, o2, g
-
-
-class _SurvLossFn(torch.autograd.Function):
-    """per-sample loss [B] = w_ifmle * ifmle_i + w_emd * emd_i, differentiable w.r.t. the predictions only."""
-
-    @staticmethod
-    def forward(ctx, x, t, e, ls, from_logits, alpha, eps, p, raw, w_ifmle, w_emd):
-        o1, o2, g = _launch(x, t, e, from_logits, ls, alpha, eps, p, raw, w_ifmle, w_emd, want_grad=True)
-        ctx.save_for_backward(g)
-        if o1 is None or o2 is None:
-            return w_emd * o2 if o1 is None else w_ifmle * o1
-        return w_ifmle * o1 + w_emd * o2
-
-    @staticmethod
-    def backward(ctx, dl):
-        (g,) = ctx.saved_tensors
-        return (dl.reshape(-1, 1) * g,) + (None,) * 10
-
-
-class _SurvObjectiveFn(torch.autograd.Function):
-    """mean_i (w_ifmle ifmle_i + w_emd emd_i) from the raw logits: ONE launch forward (``vlsa_surv_objective``: value, gradient and the
-    mean over the batch; optionally the exp of the raw logit scale), one multiplication backward."""
-
-    @staticmethod
-    def forward(ctx, x, t, e, ls, ls_is_log, alpha, eps, p, raw, w_ifmle, w_emd):
-        _need_gpu(x)
-        lib = nat.load()
-        x = x.detach().float().contiguous()
-        B, K = x.shape
-        t = t.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
-        e = e.reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
-        if t.numel() != B or e.numel() != B:
-            raise ValueError("t and e must hold one entry per sample")
-        ls = ls.detach().to(device=x.device, dtype=torch.float32).reshape(1).contiguous()
-        out = torch.empty(1 + B * K, dtype=torch.float32, device=x.device)      # objective | gradient: one allocation
-        g = out[1:].view(B, K)
-        nat.check(lib.vlsa_surv_objective(_p(x), _p(t), _p(e), B, K, 1, _p(ls), int(ls_is_log), float(alpha), float(eps), int(p), int(raw),
-                                          float(w_ifmle), float(w_emd), _p(out), _p(g), _stream()), "vlsa_surv_objective")
-        ctx.save_for_backward(g)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, dl):
-        (g,) = ctx.saved_tensors
-        return (dl * g,) + (None,) * 10
-
-
 _CONV = {"none": nat.CONV_NONE, "softmax": nat.CONV_SOFTMAX, "sigmoid": nat.CONV_SIGMOID}
 _T2I_LOSS = {"CL": nat.T2I_CL, "KL": nat.T2I_KL}
+ONE_LAUNCH_MAX_B = 4096         # vlsa_surv_objective_terms: one block walks the batch
 
 
 def _prep(x, t, e):
@@ -200,7 +135,7 @@ class SurvIFMLE(nn.Module):
 
     def forward(self, incidence_hat, t, e, cur_alpha=None):
         alpha = self.alpha if cur_alpha is None else cur_alpha
-        loss = _SurvLossFn.apply(incidence_hat, t, e, None, False, alpha, self.eps, 2, True, 1.0, 0.0)
+        loss = _LaunchFn.apply(incidence_hat, lambda x: _terms_rows(x, t, e, None, nat.CONV_NONE, nat.SURV_IFMLE, alpha, self.eps, 2, True, 1.0, 0.0))
         return _reduce(loss, self.reduction)
 
 
@@ -213,7 +148,8 @@ class SurvEMD(nn.Module):
         self.p, self.raw_distance, self.reduction = p, raw_distance, reduction
 
     def forward(self, y_hat, t, e, cur_logit_scale=10.0):
-        loss = _SurvLossFn.apply(y_hat, t, e, cur_logit_scale, False, 0.0, 1e-7, self.p, self.raw_distance, 0.0, 1.0)
+        loss = _LaunchFn.apply(y_hat, lambda x: _terms_rows(x, t, e, cur_logit_scale, nat.CONV_NONE, nat.SURV_IFMLE, 0.0, 1e-7, self.p,
+                                                           self.raw_distance, 0.0, 1.0))
         if self.reduction == "mean":
             return loss.mean()
         if self.reduction == "sum":
@@ -255,8 +191,8 @@ class SurvObjective(nn.Module):
     The keyword-only arguments select the handler's other objectives (``calc_objective_loss``, runner/vlsa_handler.py:241-258):
     ``converter='sigmoid'`` with ``weight_mle`` is the hazard family, weight_mle * SurvMLE(sigmoid(raw)) + weight_emd *
     SurvEMD(sigmoid(raw)); ``weight_t2i`` adds weight_t2i * SurvT2I(raw) in its ``t2i_loss`` ('CL' / 'KL') and ``t2i_reduction``
-    ('mean' / 'sum') form.  Still one launch (``vlsa_surv_objective_terms``) up to 4096 samples; above, the per-sample launch, the two
-    of SurvT2I and torch adds.  With the defaults the object is what it was and issues ``vlsa_surv_objective``."""
+    ('mean' / 'sum') form.  Every objective is one launch (``vlsa_surv_objective_terms``) up to 4096 samples; above, the per-sample
+    launch, the two of SurvT2I and torch adds."""
 
     def __init__(self, weight_ifmle=1.0, weight_emd=1.0, alpha=0.0, eps=1e-7, p=2, raw_distance=True, *, converter="softmax",
                  weight_mle=0.0, weight_t2i=0.0, t2i_loss="CL", t2i_reduction="mean"):
@@ -274,7 +210,6 @@ class SurvObjective(nn.Module):
         if t2i_loss not in _T2I_LOSS:
             raise NotImplementedError(f"Expected loss = CL or KL, but got {t2i_loss}.")
         self.converter, self.w_mle, self.w_t2i, self.t2i_loss, self.t2i_reduction = converter, weight_mle, weight_t2i, t2i_loss, t2i_reduction
-        self._default = converter == "softmax" and weight_t2i == 0       # (weight_mle is 0 here): today's launches, verbatim
 
     @classmethod
     def from_handler(cls, loss, loss_weight, converter):
@@ -303,8 +238,13 @@ class SurvObjective(nn.Module):
         return (_CONV[self.converter], nat.SURV_MLE if hazard else nat.SURV_IFMLE, self.alpha, self.eps, self.p, self.raw,
                 self.w_mle if hazard else self.w1, self.w2, self.w_t2i, self.t2i_loss, self.t2i_reduction)
 
-    def _forward_terms(self, raw_pred, t, e, ls, is_log):
-        if isinstance(ls, torch.Tensor) and raw_pred.is_cuda and raw_pred.dim() == 2 and raw_pred.shape[0] <= 4096:
+    def forward(self, raw_pred, t, e=None, cur_logit_scale=10.0, log_logit_scale=None):
+        """cur_logit_scale: exp(logit_scale) as the handler passes it (``net.get_logit_scale()``); log_logit_scale: the raw parameter
+        instead (exponentiated inside the launch: one kernel less per step; no gradient flows into it either way -- the reference detaches it)."""
+        if e is None:
+            t, e = t[:, 0], t[:, 1]
+        ls, is_log = (log_logit_scale, True) if log_logit_scale is not None else (cur_logit_scale, False)
+        if isinstance(ls, torch.Tensor) and raw_pred.is_cuda and raw_pred.dim() == 2 and raw_pred.shape[0] <= ONE_LAUNCH_MAX_B:
             return _LaunchFn.apply(raw_pred, lambda x: _launch_objective_terms(x, t, e, ls, is_log, self._spec()))
         if is_log:
             ls = ls.detach().exp() if isinstance(ls, torch.Tensor) else float(torch.tensor(ls).exp())
@@ -314,48 +254,17 @@ class SurvObjective(nn.Module):
             loss = loss + _LaunchFn.apply(raw_pred, lambda x: _launch_t2i(x, t, e, ls, False, t2i_loss, t2i_reduction, w_t2i))
         return loss
 
-    def forward(self, raw_pred, t, e=None, cur_logit_scale=10.0, log_logit_scale=None):
-        """cur_logit_scale: exp(logit_scale) as the handler passes it (``net.get_logit_scale()``); log_logit_scale: the raw parameter
-        instead (exponentiated inside the launch: one kernel less per step; no gradient flows into it either way -- the reference detaches it)."""
-        if e is None:
-            t, e = t[:, 0], t[:, 1]
-        ls, is_log = (log_logit_scale, True) if log_logit_scale is not None else (cur_logit_scale, False)
-        if not self._default:
-            return self._forward_terms(raw_pred, t, e, ls, is_log)
-        if isinstance(ls, torch.Tensor) and raw_pred.is_cuda and raw_pred.dim() == 2 and raw_pred.shape[0] <= 4096:
-            return _SurvObjectiveFn.apply(raw_pred, t, e, ls, is_log, self.alpha, self.eps, self.p, self.raw, self.w1, self.w2)
-        if is_log:
-            ls = ls.detach().exp() if isinstance(ls, torch.Tensor) else float(torch.tensor(ls).exp())
-        loss = _SurvLossFn.apply(raw_pred, t, e, ls, True, self.alpha, self.eps, self.p, self.raw, self.w1, self.w2)
-        return loss.mean()
-
     def value_and_grad(self, raw_pred, t, e=None, log_logit_scale=None):
         """(objective, d objective / d raw_pred) from the one launch, outside autograd -- for a caller that owns the step and starts the
         backward pass itself with ``raw_pred.backward(grad)`` (``vlsa_amd.train_step.TrainStep``): ``loss.backward()`` costs two more
-        launches (the ones_like seed and its product with the saved gradient), ~10 us of a graph-replayed step.  [B <= 4096, K] logits
-        on the GPU, the raw (log) logit scale as a tensor."""
+        launches (the ones_like seed and its product with the saved gradient), ~10 us of a graph-replayed step.  [B, K] logits on the
+        GPU, the raw (log) logit scale as a tensor."""
         if e is None:
             t, e = t[:, 0], t[:, 1]
-        if not self._default:
-            return self._value_and_grad_terms(raw_pred, t, e, log_logit_scale)
-        lib = nat.load()
-        x = raw_pred.detach().float().contiguous()
-        _need_gpu(x)
-        B, K = x.shape
-        t = t.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
-        e = e.reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
-        if t.numel() != B or e.numel() != B:
-            raise ValueError("t and e must hold one entry per sample")
-        ls = log_logit_scale.detach().to(device=x.device, dtype=torch.float32).reshape(1).contiguous()
-        out = torch.empty(1 + B * K, dtype=torch.float32, device=x.device)
-        g = out[1:].view(B, K)
-        nat.check(lib.vlsa_surv_objective(_p(x), _p(t), _p(e), B, K, 1, _p(ls), 1, float(self.alpha), float(self.eps), int(self.p),
-                                          int(self.raw), float(self.w1), float(self.w2), _p(out), _p(g), _stream()), "vlsa_surv_objective")
-        return out[0], g
-
-    def _value_and_grad_terms(self, raw_pred, t, e, log_logit_scale):
-        """``value_and_grad`` of the other objectives: the one launch up to 4096 samples, else the launches of the autograd route"""
-        if raw_pred.shape[0] <= 4096:
+        # Above ONE_LAUNCH_MAX_B samples the objectives differ, and callers rely on both: SurvIFMLE + SurvEMD without SurvT2I -- the objective
+        # this method was written for -- has only the one launch, which refuses such a batch (VlsaNativeError); the hazard family and
+        # anything with SurvT2I fall back to the launches of the autograd route.
+        if raw_pred.shape[0] <= ONE_LAUNCH_MAX_B or (self.converter == "softmax" and self.w_t2i == 0):
             return _launch_objective_terms(raw_pred, t, e, log_logit_scale, True, self._spec())
         conv, family, alpha, eps, p, raw, w_main, w_emd, w_t2i, t2i_loss, t2i_reduction = self._spec()
         rows, g = _terms_rows(raw_pred, t, e, log_logit_scale.detach().exp(), conv, family, alpha, eps, p, raw, w_main, w_emd)
